@@ -21,6 +21,11 @@ ARITHMETIC.  The top-level ``value`` is measured in the reference's own arithmet
 fp32 accumulation, ~16 mantissa bits per product, inside north_star's 1e-4 rel-L2 by 40x) is the FAST mode; its figure is the
 ``bf16x3_mode`` block of the same line, never ``value``.  ``like_for_like`` repeats which block is the fp32 one.
 
+PLAIN vs FULL.  A plain run (no ``--full``) does only what the headline needs: set-up, W warm-up steps, the K timed steps, the outputs of
+the last timed step when ``--dump-outputs DIR`` is given, and the one line (``value``, ``ms_per_step``, ``dtype`` ...; the blocks of the
+secondary legs are null).  ``--full`` adds every secondary leg: the sustained window, strong_cfg3 at N > 1, the other samplers, the
+instrumented step and its rooflines, the other arithmetic mode, the cfg5 / dcae / rccl_world1 blocks and the cpu_baseline legs.
+
 Prints ONE JSON line on rank 0.  This file parses the arguments and assembles that line; the legs live in ``benchlib/``:
 ``rollout.py`` (headline, sustained, strong cfg 3, samplers, other arithmetic mode, cfg 5, roofline rows), ``dcae.py`` (BASELINE
 configs[0] + the conv roofline row), ``cpu.py`` (the oracle-timed cpu_baseline legs: cfg 1 and cfg 2), ``rccl_world1.py`` (RCCL executed
@@ -59,15 +64,19 @@ def parse_args(argv=None):
                     "reference's scheduler loop with its EDM DPM-Solver++(2M) scheduler, N forwards; ddim = the same loop with ladcast_amd.schedulers.DDIMScheduler "
                     "(diffusers defaults, eta = 0), N forwards - BASELINE's literal '20-step DDIM'")
     ap.add_argument("--dump-output", default=None, help="rank 0 saves the (gathered) result tensor of the LAST timed step to this .pt file (tests)")
-    ap.add_argument("--cpu-forwards", type=int, default=5, help="oracle forwards timed for cfg 2's cpu_baseline after one warm-up forward; the MEDIAN is reported (0 = skip "
-                    "every cpu_baseline leg, cfg 1's too)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the LAST timed step returned (the gathered latents, or the decoded "
+                    "fields with --decode) as DIR/<name>.npy, float32; an array above 64 MB is replaced by a fixed seeded sample of its elements (DIR/<name>_sample.npy)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg (sustained window, strong_cfg3 at N > 1, other samplers, instrumented step + "
+                    "rooflines, other arithmetic mode, cfg5 / dcae / rccl_world1 blocks, cpu_baseline legs); off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--cpu-forwards", type=int, default=None, help="oracle forwards timed for cfg 2's cpu_baseline after one warm-up forward; the MEDIAN is reported (0 = skip "
+                    "every cpu_baseline leg, cfg 1's too; default 5 with --full, else 0)")
     ap.add_argument("--strong-cfg3", action="store_true", help="also run BASELINE configs[2] (a fixed ensemble of 16 members, 40 lead steps = 10 chained chunks per member) "
-                    "as an extra leg and print it as `strong_cfg3` - always on with N > 1, where it is north_star's strong-scaling point")
-    ap.add_argument("--no-kernel-timers", action="store_true", help="the timed region, sustained window and strong_cfg3 only: no instrumented step (roofline), no other "
+                    "as an extra leg and print it as `strong_cfg3` - always on with --full at N > 1, where it is north_star's strong-scaling point")
+    ap.add_argument("--no-kernel-timers", action="store_true", help="with --full: the timed region, sustained window and strong_cfg3 only: no instrumented step (roofline), no other "
                     "arithmetic mode, no dcae / cfg5 / rccl_world1 blocks")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend; nccl (= RCCL over xGMI) is the real one, "
                     "gloo only lets the N > 1 code path be dry-run on a box with fewer GPUs than ranks")
-    ap.add_argument("--no-strong-cfg3", action="store_true", help="skip the strong_cfg3 leg that N > 1 runs carry by default (tests of other fields)")
+    ap.add_argument("--no-strong-cfg3", action="store_true", help="skip the strong_cfg3 leg that --full runs at N > 1 carry (tests of other fields)")
     ap.add_argument("--collective-timeout", type=float, default=300.0, help="seconds before a rendezvous / collective is declared dead (the rank then exits non-zero)")
     ap.add_argument("--share-gpus", action="store_true", help="dry-run aid: map ranks onto the available GPUs modulo their count")
     ap.add_argument("--host-outputs", action="store_true", help="A/B aid: return every step's latents on the host as the reference's roll_out_serial does (one device "
@@ -90,9 +99,33 @@ def parse_args(argv=None):
     ap.add_argument("--no-batched-conditioning", action="store_true", help="A/B aid: evaluate the sample-independent part of the network (context refiner, conditioning "
                     "embedding, AdaLN modulation vectors) inside every network evaluation as the reference does, instead of once per chunk as one batch over the "
                     "chunk's noise levels (LaDCastTransformer3DModel.prepare_conditioning)")
-    ap.add_argument("--sustained-seconds", type=float, default=10.0, help="after the K timed steps keep stepping until this many seconds of "
-                    "back-to-back chunks have run and report that window as `sustained` (clock under sustained load); 0 = skip")
-    return ap.parse_args(argv)
+    ap.add_argument("--sustained-seconds", type=float, default=None, help="after the K timed steps keep stepping until this many seconds of "
+                    "back-to-back chunks have run and report that window as `sustained` (clock under sustained load); 0 = skip (default 10 with --full, else 0)")
+    args = ap.parse_args(argv)
+    if args.cpu_forwards is None:
+        args.cpu_forwards = 5 if args.full else 0
+    if args.sustained_seconds is None:
+        args.sustained_seconds = 10.0 if args.full else 0.0
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, name, t):
+    """--dump-outputs: `t` (what the last timed step returned) as out_dir/<name>.npy in float32 (float64 if the path returns float64).  Above
+    DUMP_MAX_BYTES a fixed sample is written instead: flat indices drawn by a generator seeded with 0 (the same for every run of the same
+    arguments), values in index order, as out_dir/<name>_sample.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    t = t.detach().to("cpu")
+    t = t.double() if t.dtype == torch.float64 else t.float()
+    if t.numel() * t.element_size() > DUMP_MAX_BYTES:
+        k = (DUMP_MAX_BYTES - (1 << 20)) // t.element_size()
+        idx = torch.randint(t.numel(), (k,), generator=torch.Generator().manual_seed(0)).sort().values
+        t, name = t.reshape(-1)[idx], name + "_sample"
+    np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
 
 
 def main():
@@ -129,13 +162,15 @@ def main():
     m, lead, R = ro.m, ro.lead, ro.R
     timed = ro.timed_region()
     elapsed = timed["elapsed"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "fields" if args.decode else "latents", timed["out"])
     sustained = ro.sustained(elapsed / args.steps) if args.sustained_seconds > 0 else None
-    strong_cfg3 = ro.strong_cfg3() if ((world > 1 or args.strong_cfg3) and not args.decode and not args.no_strong_cfg3) else None
-    extras = not args.no_kernel_timers and rank == 0 and world == 1 and not args.decode  # the secondary legs of the default N = 1 line
+    strong_cfg3 = ro.strong_cfg3() if (((world > 1 and args.full) or args.strong_cfg3) and not args.decode and not args.no_strong_cfg3) else None
+    extras = args.full and not args.no_kernel_timers and rank == 0 and world == 1 and not args.decode  # the secondary legs of the --full N = 1 line
     other_sampler, ddim_sampler, host_outputs = ro.alt_samplers() if extras else (None, None, None)
     timer = KernelTimer()
     instrumented_ms, ks, bracket = None, {}, (None, None, None)
-    if not args.no_kernel_timers and rank == 0:
+    if args.full and not args.no_kernel_timers and rank == 0:
         instrumented_ms, ks = ro.instrumented_step(timer)
         try:
             bracket = bracket_overhead(ro.hip, dev)

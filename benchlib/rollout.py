@@ -230,7 +230,7 @@ class Rollout:
         elapsed = self.max_over_ranks(elapsed)
         if a.dump_output and self.rank == 0 and last_out is not None:
             torch.save(last_out.detach().to("cpu"), a.dump_output)
-        return dict(elapsed=elapsed, step_ms=step_ms, rank_stats=rank_stats,
+        return dict(elapsed=elapsed, step_ms=step_ms, rank_stats=rank_stats, out=last_out,
                     gpu={"device_index": dev_index, "before": state_before, "during_timed_region": gpu_during, "after": state_after,
                          "note": "rank 0's GPU from sysfs (hwmon of its PCI function): one reading before the timed region, one every 50 ms during it (background thread), one "
                                  "after; two runs whose `value` differs on different boxes can be compared by the clock / power the chip held"})

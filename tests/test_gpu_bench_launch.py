@@ -37,7 +37,8 @@ def test_bench_strong_scaling_fixed_ensemble_over_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     for E, want in ((3, [2, 1]), (1, [1, 0])):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpus", "--steps", "1", "--warmup", "0",
-               "--cpu-forwards", "0", "--sustained-seconds", "0", "--no-kernel-timers", "--ensemble-size", str(E), "--solver-steps", "4", "--precision", "bf16x3"]
+               "--cpu-forwards", "0", "--sustained-seconds", "0", "--no-kernel-timers", "--ensemble-size", str(E), "--solver-steps", "4", "--precision", "bf16x3",
+               "--full"]  # (strong_cfg3 is a secondary leg: --full)
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -54,12 +55,12 @@ def test_bench_strong_scaling_fixed_ensemble_over_two_ranks():
 
 
 def test_default_line_carries_like_for_like_dcae_cfg5_and_rccl_blocks():
-    """the default `--gpus 1` line - what the driver records as BENCH_rNN.json - must carry (i) `value` in the reference's own
+    """the `--gpus 1 --full` line (every leg of the default configuration) must carry (i) `value` in the reference's own
     arithmetic (exact fp32) with the split-bf16 fast mode as its own block, `like_for_like` saying which is which; (ii) a `dcae` block (BASELINE
     configs[0] on the GPU in the three arithmetic modes, the dominant conv's roofline row, configs[0]'s cpu_baseline); (iii) a `cfg5` block; and
-    `ranks.rccl_version` from the world-size-1 RCCL child.  Reduced step counts here; every leg runs."""
+    `ranks.rccl_version` from the world-size-1 RCCL child.  Reduced step counts here; every leg runs (`--full`)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-forwards", "1", "--sustained-seconds", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-forwards", "1", "--sustained-seconds", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -96,6 +97,30 @@ def test_default_line_carries_like_for_like_dcae_cfg5_and_rccl_blocks():
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["value"] > 0 and line["gpu_over_cpu"] > 20  # north_star: >= 20x the CPU reference
     # RCCL ran for real at world size 1
     assert line["rccl_world1"]["ok"] and line["ranks"]["rccl_version"] == line["rccl_world1"]["rccl_version"] and line["ranks"]["backend"] == "none"
+
+
+def test_plain_line_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """a plain run (no --full): the headline fields only, the secondary blocks null; --dump-outputs writes what the last timed step
+    returned, the same tensor --dump-output saves"""
+    import numpy as np
+    import torch
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out, pt = tmp_path / "out", str(tmp_path / "last.pt")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out), "--dump-output", pt]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "ensemble-member-steps/sec" and line["unit"] == "member-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["steps"] == 3 and len(line["step_ms"]) == 3 and abs(line["value"] - 1 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+    for k in ("sustained", "strong_cfg3", "other_sampler", "bf16x3_mode", "cfg5", "dcae", "rccl_world1", "roofline", "cpu_baseline", "instrumented_ms_per_step"):
+        assert line[k] is None, k
+    assert sorted(os.listdir(out)) == ["latents.npy"]
+    got = np.load(out / "latents.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 1, 84, 2, 15, 30) and np.isfinite(got).all()
+    assert np.array_equal(got, torch.load(pt).numpy())
 
 
 def test_bench_rejects_mismatched_world():

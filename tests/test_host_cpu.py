@@ -285,3 +285,31 @@ def test_bare_make_builds_the_library():
     assert first.startswith("default: all"), first
     plan = subprocess.run(["make", "-n", "-B", "-C", os.path.join(ROOT, "ladcast_amd", "csrc")], capture_output=True, text=True, check=True).stdout
     assert "-o ../libladcast_hip.so" in plan and "attn_f32.hip" in plan and "conv_halo.hip" in plan
+
+
+def test_bench_plain_run_defaults_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: a plain run skips every secondary leg unless --full (an explicit value still holds); --dump-outputs writes float32
+    .npy files, and an array above the 64 MB budget becomes a seeded sample that is the same on every call"""
+    import numpy as np
+
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.cpu_forwards == 0 and a.sustained_seconds == 0 and a.steps == 3 and a.dump_outputs is None
+    a = bench.parse_args(["--full"])
+    assert a.full and a.cpu_forwards == 5 and a.sustained_seconds == 10.0
+    a = bench.parse_args(["--full", "--cpu-forwards", "0", "--sustained-seconds", "0"])
+    assert a.cpu_forwards == 0 and a.sustained_seconds == 0
+    x = torch.randn(2, 3, 5, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "d"), "latents", x)
+    y = np.load(tmp_path / "d" / "latents.npy")
+    assert y.dtype == np.float64 and np.array_equal(y, x.numpy())
+    bench.dump_outputs(str(tmp_path / "d"), "half", x.half())
+    assert np.load(tmp_path / "d" / "half.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", (1 << 20) + 4096)
+    big = torch.arange(1 << 20, dtype=torch.float32)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), "fields", big)
+        assert sorted(os.listdir(tmp_path / d)) == ["fields_sample.npy"]
+    s1, s2 = np.load(tmp_path / "s1" / "fields_sample.npy"), np.load(tmp_path / "s2" / "fields_sample.npy")
+    assert s1.dtype == np.float32 and s1.size == 1024 and np.array_equal(s1, s2) and (np.diff(s1) >= 0).all()

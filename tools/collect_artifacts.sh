@@ -26,10 +26,10 @@ if [ "${2:-all}" = pmc ]; then
   cat $O/pmc_summary_fp32.txt $O/pmc_summary.txt
   exit 0
 fi
-# the default line exactly as the driver runs it (fp32 headline + bf16x3_mode + dcae + cfg5 + rccl_world1 + both cpu_baselines)
-python3 $B --steps 20 --warmup 5 > $O/bench_default_line.json 2> $O/bench.err
-python3 $B --precision bf16x3 --steps 20 --warmup 5 $Q --no-dcae-block --no-cfg5-block --no-rccl-world1 > $O/bench_cfg2_bf16x3.json 2>> $O/bench.err
-python3 $B --precision bf16 $Q --no-dcae-block --no-cfg5-block --no-rccl-world1 > $O/bench_cfg2_bf16.json 2>> $O/bench.err
+# the full line of the default configuration (fp32 headline + bf16x3_mode + dcae + cfg5 + rccl_world1 + both cpu_baselines)
+python3 $B --full --steps 20 --warmup 5 > $O/bench_default_line.json 2> $O/bench.err
+python3 $B --full --precision bf16x3 --steps 20 --warmup 5 $Q --no-dcae-block --no-cfg5-block --no-rccl-world1 > $O/bench_cfg2_bf16x3.json 2>> $O/bench.err
+python3 $B --full --precision bf16 $Q --no-dcae-block --no-cfg5-block --no-rccl-world1 > $O/bench_cfg2_bf16.json 2>> $O/bench.err
 for P in fp32 bf16x3; do
   python3 $B --precision $P --members-per-gpu 2 --lead-steps 40 --steps 3 --warmup 1 $LEG > $O/bench_cfg3_share_2members_40leadsteps_$P.json 2>> $O/bench.err
   python3 $B --precision $P --model 1.6B --lead-steps 10 --steps 3 --warmup 1 $LEG > $O/bench_cfg4_share_1p6B_10leadsteps_$P.json 2>> $O/bench.err
