@@ -299,15 +299,25 @@ class AutoencoderDC(ModelMixin):
         """Replay one captured hipGraph per (encode | decode, input shape) instead of ~400 launches from Python.  Same kernels and
         arguments, bit-identical results.  Measured on one MI355X it buys nothing on an idle host (one frame: 5.5 ms either way - the
         ~400 small kernels, not their launches, are the time); it takes the host out of the loop when 8 ranks share one box."""
-        if flag and any(m.foreign_processor is not None for m in self.modules() if isinstance(m, SanaMultiscaleLinearAttention)):
-            raise NotImplementedError("a user-supplied DCAE attention processor runs eagerly (torch tensors): it cannot be captured into a hipGraph")
+        if flag and self._has_foreign_processor():
+            raise NotImplementedError(self._FOREIGN_NOT_CAPTURABLE)
         self.use_hip_graph = bool(flag)
         if not flag:
             self._graphs = {}
         return self
 
+    _FOREIGN_NOT_CAPTURABLE = "a user-supplied DCAE attention processor runs eagerly (torch tensors): it cannot be captured into a hipGraph"
+
+    def _has_foreign_processor(self):
+        return any(m.foreign_processor is not None for m in self.modules() if isinstance(m, SanaMultiscaleLinearAttention))
+
     def _graphed(self, key, fn, inputs):
         """fn(*static inputs) -> output tensor, kernel launches only on the current stream"""
+        if self._has_foreign_processor():
+            # a processor installed after the capture (a plain attribute: nothing tells the model) - a cached graph would replay the
+            # fused path and ignore it.  Checked here, before any capture or replay starts.
+            self._graphs = {}
+            raise NotImplementedError(self._FOREIGN_NOT_CAPTURABLE)
         key = key + (self._plan_gen, self.gemm_precision)  # generation counter, not id(): a rebuilt dict may reuse a freed id
         ent = self._graphs.get(key)
         if ent is None:

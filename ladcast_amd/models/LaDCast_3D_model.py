@@ -336,7 +336,8 @@ class LaDCastTransformer3DModel(ModelMixin):
         return self._kbias[key]
 
     def set_gemm_precision(self, mode: str):
-        """"fp32": exact-fp32 matrix cores (v_mfma_f32_32x32x2_f32).  "bf16x3": split-bf16 error-compensated
+        """"fp32": exact-fp32 matrix cores - the GEMMs on the ring kernel (gemm_bf16x3_v3_kernel<128, 0, *>:
+        v_mfma_f32_16x16x4_f32), both attention contractions on v_mfma_f32_32x32x2_f32 (attn_f32.hip).  "bf16x3": split-bf16 error-compensated
         contraction on the bf16 matrix cores (hi*hi + hi*lo + lo*hi, fp32 accumulate), ~4e-6 rel-L2 per
         forward vs fp32 -- see DESIGN.md section 4.  Applies to the token-stream GEMMs and both attention
         contractions; softmax, norms, RoPE, modulation vectors and the sampler state stay fp32 / fp64.

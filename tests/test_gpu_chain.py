@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 from oracle import pipelines as OP  # noqa: E402
 from oracle.ar_model import CONFIG_375M  # noqa: E402
 from oracle.scheduler import EDMDPMSolverMultistepScheduler as OracleScheduler  # noqa: E402
+from tests.precision_bands import check as band_check, check_all as band_check_all  # noqa: E402
 from tests.synth import make_ar, oracle_threads, rel_l2, synth_known, tiny_ar_config  # noqa: E402
 
 TOL = 1e-4
@@ -56,6 +57,7 @@ def test_full_375m_chunk_matches_oracle(fullsize_chunk_oracle):
     o = fx.ar
     g = to_hip(o, dict(CONFIG_375M))
     known, ts = fx.known, fx.ts
+    errs = {}
     for sampler, n_fwd in (("edm", 39), ("pipeline", 20)):
         if sampler == "edm":
             want, ins, outs, t_cpu = fx.want, fx.ins, fx.outs, fx.seconds
@@ -83,6 +85,7 @@ def test_full_375m_chunk_matches_oracle(fullsize_chunk_oracle):
             print(f"  network-output error per evaluation: {_fmt(e_out)}")
             assert e < tol, (sampler, mode, e)
             assert max(e_in) < tol and max(e_out) < tol_out, (sampler, mode, max(e_in), max(e_out))
+            errs[sampler, mode] = e
             # the graph-replayed chunk (what bench.py times) gives the same sample bit for bit
             g.enable_hip_graph(True)
             got_g = ensemble_AR_sampler(AutoRegressive2DPipeline(g, EDMDPMSolverMultistepScheduler()), 1, 4, 20, known_latents=known.cuda(),
@@ -90,6 +93,8 @@ def test_full_375m_chunk_matches_oracle(fullsize_chunk_oracle):
             g.enable_hip_graph(False)
             assert torch.equal(got_g, got), (sampler, mode)
         g.set_gemm_precision("fp32")
+    for sampler in ("edm", "pipeline"):
+        band_check(f"chunk_375m_{sampler}", errs[sampler, "fp32"], errs[sampler, "bf16x3"])
 
 
 def test_chunk_replays_are_bitwise_reproducible(oracle_375m):
@@ -218,6 +223,7 @@ def test_1_6b_heun_step_truncated_chunk():
     want, tc = _chained_oracle("fullsize_1p6b_truncated_chunks.npz", o, FakeAE(), t0, kw)
     del o
     assert tuple(want.shape) == (1, 1, 84, 7, 15, 30) and not torch.isnan(want).any()
+    errs = {}
     for mode in ("fp32", "bf16x3"):
         g.set_gemm_precision(mode)
         got = roll_out_serial(None, t0, AutoRegressive2DPipeline(g, EDMDPMSolverMultistepScheduler()), known_latents_override=ic, **kw)
@@ -225,6 +231,9 @@ def test_1_6b_heun_step_truncated_chunk():
         e1, e2 = rel_l2(got[:, :, :, 1:5], want[:, :, :, 1:5]), rel_l2(got[:, :, :, 5:7], want[:, :, :, 5:7])
         print(f"\n1.6B, 6 lead steps = chunk + truncated chunk, 5 forwards each (oracle {tc:.0f} s) [{mode}]: rel-L2 {e1:.2e} / {e2:.2e}")
         assert e1 < TOL and e2 < TOL, (mode, e1, e2)
+        errs[mode] = (e1, e2)
+    band_check("chunk_1p6b_5fwd", errs["fp32"][0], errs["bf16x3"][0])
+    band_check("chunk_1p6b_truncated", errs["fp32"][1], errs["bf16x3"][1])
 
 
 def test_375m_two_members_three_chained_full_size_chunks():
@@ -258,6 +267,7 @@ def test_375m_two_members_three_chained_full_size_chunks():
     d01, d12 = rel_l2(nn_(want[:, :, :, 1:5]), nn_(want[:, :, :, 5:9])), rel_l2(nn_(want[:, :, :, 5:9]), nn_(want[:, :, :, 9:13]))
     print(f"\nchunk-to-chunk change of the oracle's frames: {d01:.2e} {d12:.2e}")
     assert d01 > 1e-3 and d12 > 1e-3  # ... and so do consecutive chunks
+    errs = {}
     for mode in ("fp32", "bf16x3"):
         g.set_gemm_precision(mode).enable_hip_graph(True)
         got = roll_out_serial(None, t0, AutoRegressive2DPipeline(g, EDMDPMSolverMultistepScheduler()), known_latents_override=ic, **kw)
@@ -266,7 +276,9 @@ def test_375m_two_members_three_chained_full_size_chunks():
         per_chunk = [_rel_kept(got[:, :, :, 1 + 4 * c : 5 + 4 * c], want[:, :, :, 1 + 4 * c : 5 + 4 * c]) for c in range(3)]
         print(f"\n375M, 2 members x 12 lead steps = 3 chained chunks, 5 forwards each (oracle {tc:.0f} s) [{mode}] per-chunk rel-L2: {_fmt(per_chunk)}")
         assert max(per_chunk) < TOL, (mode, per_chunk)
+        errs[mode] = per_chunk
     g.set_gemm_precision("fp32")
+    band_check_all("chain_375m_3chunks", list(zip(errs["fp32"], errs["bf16x3"])))
 
 
 def _literal_chunk_vs_golden(golden_dir, name, cfg, members, label):
@@ -287,6 +299,7 @@ def _literal_chunk_vs_golden(golden_dir, name, cfg, members, label):
     g = to_hip(o, dict(cfg))
     del o
     known, ts = synth_known(1).cuda(), torch.tensor([2018010100]).cuda()
+    errs = {}
     for mode in ("fp32", "bf16x3"):
         g.set_gemm_precision(mode)
         rg = Rec(g)
@@ -298,12 +311,14 @@ def _literal_chunk_vs_golden(golden_dir, name, cfg, members, label):
         print(f"  network-input  error per evaluation: {_fmt(e_in)}")
         print(f"  network-output error per evaluation: {_fmt(e_out)}")
         assert e < TOL and max(e_in) < TOL and max(e_out) < TOL, (mode, e, max(e_in), max(e_out))
+        errs[mode] = e
         g.enable_hip_graph(True)
         got_g = ensemble_AR_sampler(AutoRegressive2DPipeline(g, EDMDPMSolverMultistepScheduler()), members, 4, 20, known_latents=known, timestamps=ts,
                                     sampler_type="edm", device="cuda")
         g.enable_hip_graph(False)
         assert torch.equal(got_g, got), mode
     g.set_gemm_precision("fp32")
+    band_check(f"literal_chunk_{label}", errs["fp32"], errs["bf16x3"])
 
 
 def test_1_6b_full_length_heun_chunk_vs_committed_oracle(golden_dir):
@@ -349,6 +364,7 @@ def _literal_chain_vs_golden(golden_dir, name, cfg, members, lead_hours, label, 
     assert [b - a for a, b in bounds] == frames_per_chunk
     if members > 1:
         assert rel_l2(want[:, 0], want[:, 1]) > 1e-2  # the members really differ (their own noise)
+    errs = {}
     for mode in ("fp32", "bf16x3"):
         g.set_gemm_precision(mode).enable_hip_graph(True)
         got = roll_out_serial(None, t0, AutoRegressive2DPipeline(g, EDMDPMSolverMultistepScheduler()), known_latents_override=ic, **kw)
@@ -361,7 +377,9 @@ def _literal_chain_vs_golden(golden_dir, name, cfg, members, lead_hours, label, 
         if mode == "fp32":  # eager launches = the graph-replayed chunks, bit for bit (first chunk suffices: the chain feeds on it)
             eager = roll_out_serial(None, t0, AutoRegressive2DPipeline(g, EDMDPMSolverMultistepScheduler()), known_latents_override=ic, **dict(kw, total_lead_time_hour=24))
             assert torch.equal(eager[:, :, :, 1:5], got[:, :, :, 1:5])
+        errs[mode] = per_chunk
     g.set_gemm_precision("fp32")
+    band_check_all(f"literal_chain_{label}", list(zip(errs["fp32"], errs["bf16x3"])))
 
 
 def test_cfg4_literal_1_6b_ten_lead_steps_three_chunks_vs_committed_oracle(golden_dir):

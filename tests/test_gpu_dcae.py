@@ -10,6 +10,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import dcae as OD  # noqa: E402
+from tests.precision_bands import check as band_check  # noqa: E402
 from tests.synth import make_dcae, rel_l2, synth_field, tiny_dcae_config  # noqa: E402
 
 
@@ -210,6 +211,13 @@ def test_tiny_dcae_matches_oracle_and_pin(golden_dir):
     assert zg.shape == zo.shape and rel_l2(zg.cpu(), zo) < 2e-5
     yg = g.decode(zo.cuda()).sample
     assert yg.shape == yo.shape == (2, 8, 48, 64) and rel_l2(yg.cpu(), yo) < 2e-5
+    g.set_gemm_precision("bf16x3")
+    try:
+        zb, yb = g.encode(f.cuda(), static_conditioning_tensor=st.cuda()).latent, g.decode(zo.cuda()).sample
+    finally:
+        g.set_gemm_precision("fp32")
+    band_check("tiny_dcae_encode", rel_l2(zg.cpu(), zo), rel_l2(zb.cpu(), zo))
+    band_check("tiny_dcae_decode", rel_l2(yg.cpu(), yo), rel_l2(yb.cpu(), yo))
     full = g(f.cuda(), static_conditioning_tensor=st.cuda(), return_static=True).sample
     assert full.shape == (2, 13, 48, 64)
     pin = np.load(os.path.join(golden_dir, "oracle_pins.npz"))
@@ -239,12 +247,13 @@ def test_full_dcae_single_frame_all_modes(full_dcae_oracle):
     with torch.no_grad(), OA.reference_autocast("cuda"):
         a_enc = rel_l2(d.model.encode(d.f, static_conditioning_tensor=d.st).latent.float(), d.z)
         a_dec = rel_l2(d.model.decode(d.z).sample.float(), d.y)
+    errs = {}
     for mode in ("fp32", "bf16x3", "bf16"):
         g.set_gemm_precision(mode)
         zg = g.encode(d.f.cuda(), static_conditioning_tensor=d.st.cuda()).latent
         yg = g.decode(d.z.cuda()).sample
         assert zg.shape == (1, 84, 15, 30) and yg.shape == (1, 84, 120, 240)
-        ez, ey = rel_l2(zg.cpu(), d.z), rel_l2(yg.cpu(), d.y)
+        ez, ey = errs[mode] = rel_l2(zg.cpu(), d.z), rel_l2(yg.cpu(), d.y)
         print(f"\nfull DCAE, one frame [{mode}]: encode rel-L2 {ez:.2e}, decode rel-L2 {ey:.2e}" +
               (f" (oracle under autocast: {a_enc:.2e} / {a_dec:.2e})" if mode == "bf16" else ""))
         if mode == "bf16":
@@ -254,6 +263,9 @@ def test_full_dcae_single_frame_all_modes(full_dcae_oracle):
             assert ez < 5e-5 and ey < tolerance(mode, "dcae"), (mode, ez, ey)
         if mode == "fp32":  # decode of its own latent, the round trip of configs[0]
             assert rel_l2(g.decode(zg).sample.cpu(), d.y) < 1e-4
+    g.set_gemm_precision("fp32")
+    band_check("dcae_full_encode", errs["fp32"][0], errs["bf16x3"][0])
+    band_check("dcae_full_decode", errs["fp32"][1], errs["bf16x3"][1])
 
 
 def test_decode_latent_ens_and_error_conventions():
@@ -588,6 +600,7 @@ def test_dc_ae_ray_1024_shape_one_frame():
         zo = o.encode(f, static_conditioning_tensor=st).latent
         yo = o.decode(zo).sample
     assert zo.shape == (1, 1024, 6, 12) and yo.shape == (1, 84, 48, 96)
+    errs = {}
     for mode in ("fp32", "bf16x3"):
         g.set_gemm_precision(mode)
         zg = g.encode(f.cuda(), static_conditioning_tensor=st.cuda()).latent
@@ -596,6 +609,10 @@ def test_dc_ae_ray_1024_shape_one_frame():
         print(f"\nDC_AE_ray_1024 shape, one 48 x 96 frame [{mode}]: encode rel-L2 {ez:.2e}, decode rel-L2 {ey:.2e}")
         assert zg.shape == zo.shape and yg.shape == yo.shape
         assert ez < 1e-4 and ey < 1e-4, (mode, ez, ey)
+        errs[mode] = (ez, ey)
+    g.set_gemm_precision("fp32")
+    band_check("dcae_ray1024_encode", errs["fp32"][0], errs["bf16x3"][0])
+    band_check("dcae_ray1024_decode", errs["fp32"][1], errs["bf16x3"][1])
 
 
 

@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 from oracle import pipelines as OP  # noqa: E402
 from oracle.ar_model import CONFIG_375M  # noqa: E402
 from oracle.scheduler import EDMDPMSolverMultistepScheduler as OracleScheduler  # noqa: E402
+from tests.precision_bands import check as band_check, check_all as band_check_all  # noqa: E402
 from tests.synth import make_ar, rel_l2, synth_known, tiny_ar_config  # noqa: E402
 
 TOL = 1e-4
@@ -45,6 +46,12 @@ def test_tiny_forward_matches_oracle(tiny_pair, B, R, Bt):
     assert rel_l2(got.cpu(), want) < 2e-5
     got2 = g(x.cuda(), t.cuda(), known.cuda(), time_elapsed=ts.cuda(), return_dict=False)[0]
     assert torch.equal(got, got2)  # deterministic, workspace reuse is clean
+    g.set_gemm_precision("bf16x3")
+    try:
+        got3 = g(x.cuda(), t.cuda(), known.cuda(), time_elapsed=ts.cuda()).sample
+    finally:
+        g.set_gemm_precision("fp32")
+    band_check("tiny_forward", rel_l2(got.cpu(), want), rel_l2(got3.cpu(), want))
 
 
 def test_hip_graph_replay_is_bitwise_equal_to_eager(tiny_pair):
@@ -171,6 +178,7 @@ def test_full_375m_forward_all_modes_one_and_two_members(oracle_375m):
     g = to_hip(o, dict(CONFIG_375M))
     known, ts = synth_known(1), torch.tensor([2018010100])
     cases = [(1, 1.0955067, 3), (1, -1.553652, 3), (2, 0.3, 5)]
+    bands = []
     for i, (B, t, seed) in enumerate(cases):
         x = torch.randn(B, 84, 4, 15, 30, generator=torch.Generator().manual_seed(seed))
         kn = known.expand(B, -1, -1, -1, -1)
@@ -195,7 +203,9 @@ def test_full_375m_forward_all_modes_one_and_two_members(oracle_375m):
         assert errs["bf16"] > 1e-5  # the single-term mode is really on
         if e_auto is not None:
             assert errs["bf16"] <= e_auto, (errs, e_auto)
+        bands.append((errs["fp32"], errs["bf16x3"]))
     g.set_gemm_precision("fp32")
+    band_check_all("forward_375m", bands)
 
 
 @pytest.mark.parametrize("sampler_type", ["edm", "pipeline"])
@@ -213,6 +223,12 @@ def test_tiny_sampler_chunk_matches_oracle(tiny_pair, sampler_type):
     # sharding property: member 2 alone == member 2 of the full ensemble (seed-by-member noise)
     part = ensemble_AR_sampler(gpipe, 1, 4, 6, known_latents=known.cuda(), timestamps=ts.cuda(), sampler_type=sampler_type, device="cuda", member_ids=[2])
     assert rel_l2(part.cpu(), got[2:3].cpu()) < 1e-5
+    g.set_gemm_precision("bf16x3")
+    try:
+        got3 = ensemble_AR_sampler(gpipe, 3, 4, 6, known_latents=known.cuda(), timestamps=ts.cuda(), sampler_type=sampler_type, device="cuda")
+    finally:
+        g.set_gemm_precision("fp32")
+    band_check(f"tiny_chunk_{sampler_type}", rel_l2(got.cpu(), want), rel_l2(got3.cpu(), want))
 
 
 def test_stochastic_churn_chunk_matches_oracle(tiny_pair):
@@ -282,12 +298,14 @@ def test_full_1_6b_forward_matches_oracle_both_modes():
     with torch.no_grad():
         want = o(x, torch.tensor([0.3]), known, time_elapsed=ts).sample
     del o
+    errs = {}
     for mode, tol in (("fp32", 2e-5), ("bf16x3", 3e-5)):
         g.set_gemm_precision(mode)
         got = g(x.cuda(), torch.tensor([0.3]).cuda(), known.cuda(), time_elapsed=ts.cuda()).sample
-        e = rel_l2(got.cpu(), want)
+        e = errs[mode] = rel_l2(got.cpu(), want)
         print(f"1.6B {mode} forward rel-L2 {e:.2e}")
         assert e < tol, (mode, e)
+    band_check("forward_1p6b", errs["fp32"], errs["bf16x3"])
 
 
 def test_scheduler_indexing_is_bit_exact():

@@ -1066,3 +1066,46 @@ def test_attention_split_ignores_stale_lds(hip):
                 want = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, S, D)
                 assert torch.isfinite(out).all(), (poison, B, S, H, one_term)
                 assert rel(out, want) < (1e-2 if one_term else 2e-5)
+
+
+# -- the ring kernel's scalar epilogue (gemm_v3_common.inc tile_epilogue, P.vec4 == 0) -------------------------------------------------
+SCALAR_EPI_CASES = [  # (M, N, K, batch, ldc, col0, gate_bs, act): each breaks one condition of the 16-byte epilogue
+    (300, 258, 128, 1, 258, 0, 0, 0),  # N % 4 != 0, C contiguous, no gate
+    (257, 260, 192, 2, 263, 1, 0, 1),  # C an unaligned slab (column offset 1) of rows of odd stride; in-place residual
+    (200, 256, 128, 2, 256, 0, 258, 3),  # gate rows 258 apart (gate_bs % 4 != 0)
+]
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16x3", "bf16"])
+@pytest.mark.parametrize("M,N,K,B,ldc,col0,gate_bs,act", SCALAR_EPI_CASES)
+def test_ring_gemm_scalar_epilogue(hip, mode, M, N, K, B, ldc, col0, gate_bs, act):
+    """The ring kernel's generic epilogue takes its scalar branch when N % 4 != 0 or C / bias / gate / R break the 16-byte rule (every
+    other ring-kernel case here has N, ldc and the C offset divisible by 4).  Exact fp32 (the ring kernel: K % 32 == 0, contiguous
+    weight, 16-byte operand rows), split-bf16 and single-term bf16 (pre-split / bf16 operand rows: only the ring kernel takes them) -
+    bias + activation + per-batch gate + residual, against fp64; the columns outside the slab keep their bits."""
+    A, W, b = rnd(B, M, K, seed=61), rnd(N, K, seed=62) / math.sqrt(K), rnd(N, seed=63)
+    gate = rnd(B, gate_bs, seed=64)[:, :N] if gate_bs else None
+    buf = rnd(B, M, ldc, seed=65)
+    if mode == "fp32":
+        Ad, Wd, flags, ao, wo = dev(A), dev(W), 0, A.double(), W.double()
+    elif mode == "bf16x3":
+        Ad, Wd, flags = hip.pack_weight_bf16x2(dev(A).reshape(B * M, K)), hip.pack_weight_bf16x2(dev(W)), hip.GEMM_A_SPLIT
+        (ah, al), (wh, wl) = _bf16_split(A), _bf16_split(W)
+    else:
+        Ad, Wd, flags = dev(_bf16_rows(A)), hip.pack_weight_bf16(dev(W)), hip.GEMM_A_SPLIT | hip.GEMM_BF16_1TERM
+        ao, wo = A.bfloat16().double(), W.bfloat16().double()
+    v = (ah @ wh.T + ah @ wl.T + al @ wh.T if mode == "bf16x3" else ao @ wo.T) + b.double()
+    v = [v, F.silu(v), F.gelu(v, approximate="tanh"), F.relu(v)][act]
+    if gate is not None:
+        v = v * gate[:, None, :].double()
+    want = buf.clone().double()
+    want[:, :, col0 : col0 + N] += v  # the residual is C itself (in place)
+    d_buf = dev(buf).reshape(-1)
+    Cv = d_buf[col0:]  # data_ptr offset by col0 floats
+    gd = dev(rnd(B, gate_bs, seed=64)) if gate_bs else None
+    hip.gemm_grouped([hip.gemm_problem(Ad, Wd, Cv, M=M, N=N, K=K, batch=B, a_bs=M * K, ldc=ldc, c_bs=M * ldc, bias=dev(b),
+                                       gate=gd, gate_bs=gate_bs, R=Cv, ldr=ldc, r_bs=M * ldc, act=act, flags=flags)],
+                     split_bf16=mode != "fp32")
+    got = d_buf.cpu().reshape(B, M, ldc)
+    assert rel(got[:, :, col0 : col0 + N], want[:, :, col0 : col0 + N]) < (2e-6 if mode == "fp32" else 1e-6 if mode == "bf16x3" else 1e-5), mode
+    assert torch.equal(got[:, :, :col0], buf[:, :, :col0]) and torch.equal(got[:, :, col0 + N :], buf[:, :, col0 + N :])  # outside the slab

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from tests.precision_bands import check as band_check, check_all as band_check_all  # noqa: E402
 from tests.synth import ToyNet  # noqa: E402
 
 
@@ -65,6 +66,7 @@ def test_product_transformer_reproduces_the_reference_forward_code(golden_dir):
     m = LaDCastTransformer3DModel.from_config(cfg)
     m.load_state_dict(make_ar(cfg).state_dict(), strict=True)
     m = m.cuda().eval()
+    errs = {}
     for prec, tol in (("fp32", 2e-5), ("bf16x3", 5e-5)):
         m.set_gemm_precision(prec)
         for name, (B, R, Bt, stamp) in {"a": (2, 4, 1, 2018010100), "b": (1, 1, 1, 2019063012), "c": (3, 2, 3, None)}.items():
@@ -72,8 +74,11 @@ def test_product_transformer_reproduces_the_reference_forward_code(golden_dir):
             te = None if stamp is None else torch.tensor([stamp]).cuda()
             y = m(x, torch.linspace(-1.2, 1.0, Bt).cuda(), synth_known(B).cuda(), time_elapsed=te).sample.double().flatten().cpu()
             want = torch.from_numpy(z[name]).double()
-            assert ((y[::7] - want).norm() / want.norm()).item() < tol, (prec, name)
+            e = errs[prec, name] = ((y[::7] - want).norm() / want.norm()).item()
+            assert e < tol, (prec, name)
             assert abs(y.norm().item() / float(z[name + "_norm"]) - 1) < tol
+    m.set_gemm_precision("fp32")
+    band_check_all("pin_ar_forward", [(errs["fp32", n], errs["bf16x3", n]) for n in ("a", "b", "c")])
 
 
 def test_product_nope_reproduces_the_reference_forward_code(golden_dir):
@@ -90,11 +95,14 @@ def test_product_nope_reproduces_the_reference_forward_code(golden_dir):
     m = m.cuda().eval()
     x = torch.randn(2, 84, 4, 15, 30, generator=torch.Generator().manual_seed(3)).cuda()
     want = torch.from_numpy(z["nope"]).double()
+    errs = {}
     for prec, tol in (("fp32", 2e-5), ("bf16x3", 5e-5), ("bf16", 5e-3)):
         m.set_gemm_precision(prec)
         y = m(x, torch.tensor([0.3]).cuda(), synth_known(2).cuda(), time_elapsed=torch.tensor([2018010100]).cuda()).sample.double().flatten().cpu()
-        assert ((y[::7] - want).norm() / want.norm()).item() < tol, prec
+        errs[prec] = ((y[::7] - want).norm() / want.norm()).item()
+        assert errs[prec] < tol, prec
     m.set_gemm_precision("fp32")
+    band_check("pin_nope", errs["fp32"], errs["bf16x3"])
 
 
 def test_product_patch_sizes_reproduce_the_reference_forward_code(golden_dir):
@@ -181,6 +189,7 @@ def test_product_dcae_reproduces_the_reference_forward_code(golden_dir):
     g.load_state_dict(make_dcae(cfg).state_dict(), strict=True)
     g = g.cuda().eval()
     f, st = synth_field(2, 8, 48, 64).cuda(), synth_field(1, 5, 48, 64, seed=1).cuda()
+    errs = {}
     for prec, tol in (("fp32", 2e-5), ("bf16x3", 5e-5)):
         g.set_gemm_precision(prec)
         lat = g.encode(f, static_conditioning_tensor=st).latent
@@ -188,6 +197,10 @@ def test_product_dcae_reproduces_the_reference_forward_code(golden_dir):
         rec = g.decode(zz, return_static=True).sample
         plain = g.decode(zz).sample
         assert _rel(lat, torch.from_numpy(z["z"])) < tol and _rel(rec, torch.from_numpy(z["y"])) < tol and _rel(plain, torch.from_numpy(z["y_nostatic"])) < tol
+        errs[prec] = (_rel(lat, torch.from_numpy(z["z"])), _rel(rec, torch.from_numpy(z["y"])))
+    g.set_gemm_precision("fp32")
+    band_check("pin_dcae_encode", errs["fp32"][0], errs["bf16x3"][0])
+    band_check("pin_dcae_decode", errs["fp32"][1], errs["bf16x3"][1])
 
 
 def test_product_dcae_without_a_full_resolution_stage_reproduces_the_reference_forward_code(golden_dir):
@@ -206,18 +219,21 @@ def test_product_dcae_without_a_full_resolution_stage_reproduces_the_reference_f
     g = g.cuda().eval()
     f, st = synth_field(2, 8, 48, 64).cuda(), synth_field(1, 5, 48, 64, seed=1).cuda()
     z0, y0 = torch.from_numpy(z["z_layers0"]), torch.from_numpy(z["y_layers0"])
+    errs = {}
     for prec, tol in (("fp32", 2e-5), ("bf16x3", 5e-5), ("bf16", 2e-2)):
         g.set_gemm_precision(prec)
         lat = g.encode(f, static_conditioning_tensor=st).latent
         rec = g.decode(z0.cuda(), return_static=True).sample
         plain = g.decode(z0.cuda()).sample
-        e1, e2 = _rel(lat, z0), _rel(rec, y0)
+        e1, e2 = errs[prec] = _rel(lat, z0), _rel(rec, y0)
         print(f"\nDC-AE without a full-resolution stage [{prec}]: encode {e1:.2e}, decode {e2:.2e}")
         assert lat.shape == z0.shape and rec.shape == y0.shape and e1 < tol and e2 < tol, (prec, e1, e2)
         assert plain.shape == (2, 8, 48, 64) and torch.equal(plain, rec[:, :8])  # the static channels are dropped by the same kernel
         g.enable_hip_graph(True)
         assert torch.equal(g.encode(f, static_conditioning_tensor=st).latent, lat) and torch.equal(g.decode(z0.cuda(), return_static=True).sample, rec)
         g.enable_hip_graph(False)
+    band_check("pin_dcae_layers0_encode", errs["fp32"][0], errs["bf16x3"][0])
+    band_check("pin_dcae_layers0_decode", errs["fp32"][1], errs["bf16x3"][1])
     # the interpolate form of the same conv_out (nearest x2, conv at the output width, no shortcut) against the oracle
     cfg_i = dict(cfg, upsample_block_type="interpolate")
     o = make_dcae(cfg_i)
@@ -251,17 +267,20 @@ def test_product_timestep_conditioned_dcae_reproduces_the_reference_forward_code
     f, st = synth_field(2, 8, 48, 64).cuda(), synth_field(1, 5, 48, 64, seed=1).cuda()
     tt = torch.tensor([0.3, 1.7]).cuda()
     zt, yt = torch.from_numpy(z["z_temb"]), torch.from_numpy(z["y_temb"])
+    errs = {}
     for prec, tol in (("fp32", 2e-5), ("bf16x3", 5e-5), ("bf16", 2e-2)):
         g.set_gemm_precision(prec)
         lat = g.encode(f, temb=tt, static_conditioning_tensor=st).latent
         rec = g.decode(zt.cuda(), temb=tt, return_static=True).sample
-        e1, e2 = _rel(lat, zt), _rel(rec, yt)
+        e1, e2 = errs[prec] = _rel(lat, zt), _rel(rec, yt)
         print(f"\ntimestep-conditioned tiny DC-AE [{prec}]: encode {e1:.2e}, decode {e2:.2e}")
         assert e1 < tol and e2 < tol, (prec, e1, e2)
         g.enable_hip_graph(True)
         assert torch.equal(g.encode(f, temb=tt, static_conditioning_tensor=st).latent, lat) and torch.equal(g.decode(zt.cuda(), temb=tt, return_static=True).sample, rec)
         g.enable_hip_graph(False)
     g.set_gemm_precision("fp32")
+    band_check("pin_dcae_temb_encode", errs["fp32"][0], errs["bf16x3"][0])
+    band_check("pin_dcae_temb_decode", errs["fp32"][1], errs["bf16x3"][1])
     full = g(f, time_elapsed=tt, static_conditioning_tensor=st, return_static=True).sample
     assert _rel(full, yt) < 5e-5  # decode of its OWN latent: both halves' errors
     with torch.no_grad():  # an already-embedded temb (embedded_t=True), as AutoencoderDC.forward hands it to encode / decode

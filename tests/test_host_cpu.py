@@ -313,3 +313,25 @@ def test_bench_plain_run_defaults_and_output_dump(tmp_path, monkeypatch):
         assert sorted(os.listdir(tmp_path / d)) == ["fields_sample.npy"]
     s1, s2 = np.load(tmp_path / "s1" / "fields_sample.npy"), np.load(tmp_path / "s2" / "fields_sample.npy")
     assert s1.dtype == np.float32 and s1.size == 1024 and np.array_equal(s1, s2) and (np.diff(s1) >= 0).all()
+
+
+def test_dcae_graph_cache_refuses_a_processor_installed_after_capture():
+    """a foreign DC-AE attention processor assigned while hipGraph mode is on (after a capture: a plain attribute, nothing tells the model) -
+    the next graphed call drops every cached graph and raises what enable_hip_graph(True) raises, before it captures or replays anything"""
+    from ladcast_amd.models import AutoencoderDC, SanaMultiscaleAttnProcessor2_0
+    from ladcast_amd.models.DCAE import SanaMultiscaleLinearAttention
+    from tests.synth import tiny_dcae_config
+
+    g = AutoencoderDC.from_config(tiny_dcae_config())
+    g.enable_hip_graph(True)
+    g._graphs = {("enc", 1): "a captured graph"}
+    attn = next(m for m in g.modules() if isinstance(m, SanaMultiscaleLinearAttention))
+    attn.processor = lambda attn, hidden_states, gate=None: hidden_states
+    ran = []
+    with pytest.raises(NotImplementedError, match="cannot be captured"):
+        g._graphed(("enc", 1), lambda *a: ran.append(a), [])
+    assert g._graphs == {} and not ran
+    with pytest.raises(NotImplementedError, match="cannot be captured"):
+        g.enable_hip_graph(True)
+    attn.processor = SanaMultiscaleAttnProcessor2_0()
+    g.enable_hip_graph(False)
