@@ -496,6 +496,56 @@ int ldc_ensemble_scores(const float* forecast, long long member_stride, long lon
                         int nan_channel, float* out, float* skill_map, float* spread_map, void* workspace,
                         long long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,
+ * ladcast/evaluate/track.py:151-335 (round_to_grid / select_box / find_local_minimum / track_first_n_steps), run on the
+ * xarray dataset that ladcast/pipelines/utils.py:83-246 (latent_ens_to_xarr) decodes into: the decoded frames stay on the
+ * device, only the tracker's channels are gathered, the ensemble mean is taken on the device and every track runs in one
+ * launch.  The grid is two ASCENDING fp64 coordinate arrays built on the host exactly as the reference builds them
+ * (lat = np.arange(-88.5, 90 + 1e-6, 1.5), 120 rows; lon = np.arange(0, 358.5 + 1e-6, 1.5), 240 columns); fields are fp32
+ * [H][W] planes, row = latitude.  Box bounds are index ranges found by comparing against those arrays, and the coordinate
+ * arithmetic rounds as Python's float ops do (Python's `%` included).  H, W <= LDC_TRACK_MAX_GRID.
+ * ------------------------------------------------------------------------- */
+#define LDC_TRACK_MAX_CHANNELS 8
+#define LDC_TRACK_MAX_BOXES 8 /* entries of inner_box_sizes */
+#define LDC_TRACK_MAX_INNER 30 /* degrees, per inner box size */
+#define LDC_TRACK_MAX_GRID 1024
+/* Channel gather with the inverse normalisation of decode_latent_ens (pipelines/utils.py:51-80):
+ *   out[b][t_off + t][k][p] = (x[b*sb + t*st + channels[k]*sc + p] / target_std) * std[channels[k]] + mean[channels[k]]
+ * for b < B, t < T, k < n_ch, p < HW; out is (B, T_total, n_ch, HW), so decoding in frame batches fills one buffer.  x is the
+ * decoder's output in any layout with a contiguous HW plane: (B, C, T, HW) or the frame-major (B*T, C, HW) the decoder returns.
+ * Same operations in the same order as ldc_chan_affine(inverse=1): bit-equal to decode_latent_ens(...)[:, channels].
+ * `channels` is a HOST array of n_ch <= LDC_TRACK_MAX_CHANNELS indices (copied into the launch); mean / std are device vectors
+ * indexed by channel. */
+int ldc_track_gather(const float* x, long long sb, long long st, long long sc, int B, int T, long long HW, const int* channels,
+                     int n_ch, const float* mean, const float* std_, float target_std, float* out, int T_total, int t_off,
+                     void* stream);
+/* out[i] = np.nanmean over e < E of x[e*member_stride + i], i < n (fp32, the reference's ds.mean(dim="idx")): NaNs skipped, the
+ * sum taken in member order, one division by the count (NaN where every member is NaN). */
+int ldc_track_nanmean(const float* x, long long member_stride, int E, long long n, float* out, void* stream);
+/* track_first_n_steps for n_tracks tracks, one wave each, every step and every inner box size in one launch.
+ *   track e, frame f: the MSLP plane at fields + e*track_stride + f*frame_stride + mslp_off, the Z700 plane at ... + z_off;
+ *   frame f = lead 6 h * f, frame 0 the initial condition (read by no step).
+ *   lat0 / lon0 [n_tracks]: the start, already round_to_grid'ed on the host (lon0 may be 360.0).
+ *   inner_box_sizes: HOST array of n_boxes <= LDC_TRACK_MAX_BOXES sizes, each in [0, LDC_TRACK_MAX_INNER] degrees.
+ *   enforce_msl = 0: lsm [H][W] (land-sea mask, nearest lookup with pandas' rule) picks MSLP (< 0.5) or not, then Z700 if MSLP
+ *   did not move the track; z_off >= 0 and lsm are required.  enforce_msl != 0: MSLP only (lsm, z_off unused).
+ *   out_lat / out_lon [n_tracks][n_steps + 1] fp64: the track, step 0 = the start.
+ *   out_code [n_tracks][n_steps]: per step 0 = stayed (the reference warns), 1 + k = moved on MSLP with box k,
+ *   1 + n_boxes + k = moved on Z700 with box k.
+ * LDC_ERR_UNSUPPORTED when n_boxes or an inner size is above its cap (nothing is launched). */
+int ldc_track_storms(const float* fields, long long track_stride, long long frame_stride, long long mslp_off, long long z_off,
+                     const float* lsm, const double* lat, int H, const double* lon, int W, const double* lat0,
+                     const double* lon0, int n_tracks, int n_steps, const int* inner_box_sizes, int n_boxes, int enforce_msl,
+                     double* out_lat, double* out_lon, int* out_code, void* stream);
+/* A batch of single find_local_minimum calls (track.py:173-238), so the search can be pinned apart from the track loop:
+ * query q searches the plane fields + field_idx[q]*field_stride around (lat0[q], lon0[q]) with inner size inner[q] (device arrays).
+ * found[q] = 1 -> (out_lat, out_lon, out_val)[q] = the reference's (la, lo, v); 0 -> the reference returns None;
+ * LDC_ERR_UNSUPPORTED -> inner[q] outside [0, LDC_TRACK_MAX_INNER], not searched (the host binding refuses those before launch). */
+int ldc_track_local_min(const float* fields, long long field_stride, const int* field_idx, const double* lat, int H,
+                        const double* lon, int W, const double* lat0, const double* lon0, const int* inner, int n_queries,
+                        int* found, double* out_lat, double* out_lon, float* out_val, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,10 @@ def _load():
         "ldc_pixel_unshuffle_shortcut": (I, [P, P, P, I, I, I, I, I, P]),
         "ldc_pixel_shuffle_shortcut": (I, [P, P, P, I, I, I, I, I, P]),
         "ldc_chan_regroup": (I, [P, P, L, I, I, P]),
+        "ldc_track_gather": (I, [P, L, L, L, I, I, L, POINTER(c_int), I, P, P, F, P, I, I, P]),
+        "ldc_track_nanmean": (I, [P, L, I, L, P, P]),
+        "ldc_track_storms": (I, [P, L, L, L, L, P, P, I, P, I, P, P, I, I, POINTER(c_int), I, I, P, P, P, P]),
+        "ldc_track_local_min": (I, [P, L, P, P, I, P, I, P, P, P, I, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -536,6 +540,39 @@ def temb_modulate(temb, te, *, B, D, te_rows):
 def chan_affine(x, y, mean, std, target_std, *, outer, C, inner, inverse):
     _dev(x, y, mean, std)
     _check(lib.ldc_chan_affine(_p(x), _p(y), _p(mean), _p(std), target_std, outer, C, inner, int(inverse), _stream()), "ldc_chan_affine")
+
+
+TRACK_MAX_CHANNELS, TRACK_MAX_BOXES, TRACK_MAX_INNER, TRACK_MAX_GRID = 8, 8, 30, 1024  # LDC_TRACK_MAX_* of ladcast_hip.h
+
+
+def _int_array(values):
+    return (c_int * len(values))(*[int(v) for v in values])
+
+
+def track_gather(x, out, channels, mean, std, *, sb, st, sc, B, T, HW, T_total, t_off, target_std=1.0):
+    """out (B, T_total, len(channels), HW)[:, t_off:t_off + T] = inverse-normalised channels of x (ldc_track_gather)"""
+    _dev(x, out, mean, std)
+    _check(lib.ldc_track_gather(_p(x), sb, st, sc, B, T, HW, _int_array(channels), len(channels), _p(mean), _p(std), float(target_std),
+                                _p(out), T_total, t_off, _stream()), "ldc_track_gather")
+
+
+def track_nanmean(x, out, *, member_stride, E, n):
+    _dev(x, out)
+    _check(lib.ldc_track_nanmean(_p(x), member_stride, E, n, _p(out), _stream()), "ldc_track_nanmean")
+
+
+def track_storms(fields, lat, lon, lat0, lon0, out_lat, out_lon, out_code, *, track_stride, frame_stride, mslp_off, z_off, lsm, H, W,
+                 n_tracks, n_steps, inner_box_sizes, enforce_msl):
+    _dev(fields, lat, lon, lat0, lon0, out_lat, out_lon, out_code, lsm)
+    _check(lib.ldc_track_storms(_p(fields), track_stride, frame_stride, mslp_off, z_off, _p(lsm), _p(lat), H, _p(lon), W, _p(lat0), _p(lon0),
+                                n_tracks, n_steps, _int_array(inner_box_sizes), len(inner_box_sizes), int(bool(enforce_msl)), _p(out_lat),
+                                _p(out_lon), _p(out_code), _stream()), "ldc_track_storms")
+
+
+def track_local_min(fields, field_idx, lat, lon, lat0, lon0, inner, found, out_lat, out_lon, out_val, *, field_stride, H, W, n_queries):
+    _dev(fields, field_idx, lat, lon, lat0, lon0, inner, found, out_lat, out_lon, out_val)
+    _check(lib.ldc_track_local_min(_p(fields), field_stride, _p(field_idx), _p(lat), H, _p(lon), W, _p(lat0), _p(lon0), _p(inner), n_queries,
+                                   _p(found), _p(out_lat), _p(out_lon), _p(out_val), _stream()), "ldc_track_local_min")
 
 
 def edm_scale_f64_to_f32(x, c_in, out):
