@@ -196,6 +196,17 @@ int ldc_attn_fwd(const float* Q, const float* K, const float* V, float* O, int B
 long long ldc_attn_fwd_workspace_bytes(void);
 int ldc_attn_fwd_ws(const float* Q, const float* K, const float* V, float* O, int B, int S, int H, int ld_qkv, long long qkv_bs,
                     int ldo, long long o_bs, const float* key_bias, void* workspace, long long workspace_bytes, void* stream);
+/* Fewer queries than keys: the queries are the first Sq of the S token rows (1 <= Sq <= S), keys and values are all S rows.  Rows
+ * [0, Sq) of O are written, rows >= Sq of O are not touched.  For a caller whose last Sq.. rows are only needed as keys / values - the
+ * last single-stream block of the model, whose conditioning rows no later layer reads.  Work units are query blocks of Sq x heads x
+ * batch, and every choice made from the unit count (balanced cut, wave groups) is made from that number, so the results of rows [0, Sq)
+ * agree with the full call's to fp32 rounding, not bit for bit.  Sq == S is exactly ldc_attn_fwd / ldc_attn_fwd_ws (same bits); the
+ * workspace is the same one. */
+int ldc_attn_fwd_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                       long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* stream);
+int ldc_attn_fwd_ws_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                          long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace, long long workspace_bytes,
+                          void* stream);
 
 /* (ABI 2: the second-generation split attention - ldc_attn_pack_bf16x3 / ldc_attn_fwd_packed_bf16x3 / ldc_attn_packed_bytes, a
  * pack pass writing LDS tile images + the attention on them - was removed; ldc_attn_qkv_prepare_split / the fused QKV epilogue +
@@ -260,6 +271,13 @@ int ldc_attn_fwd_split(const float* Q, const float* K, const float* V, float* O,
                        long long qkv_bs, int ldo, long long o_bs, const float* key_bias, int flags, void* workspace,
                        long long workspace_bytes, void* stream);
 /* key_bias: as ldc_attn_fwd's, but 32 * ceil(S / 32) floats (16-byte aligned; entries past S are ignored). */
+/* Fewer queries than keys, as ldc_attn_fwd_qrows: queries = token rows [0, Sq), keys / values = all S rows, rows >= Sq of O untouched (in
+ * every output format).  The units - and with them the choice of the persistent form and the workspace it asks for - are query blocks of
+ * Sq x heads x batch.  Sq == S is exactly ldc_attn_fwd_split / ldc_attn_fwd_split_workspace_bytes. */
+long long ldc_attn_fwd_split_qrows_workspace_bytes(int B, int S, int Sq, int H);
+int ldc_attn_fwd_split_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                             long long qkv_bs, int ldo, long long o_bs, const float* key_bias, int flags, void* workspace,
+                             long long workspace_bytes, void* stream);
 
 /* In-place per-head RMSNorm(128, eps, weight) on q and k followed by the
  * adjacent-pair rotary embedding (cos/sin tables [rows][128], NULL = no RoPE),

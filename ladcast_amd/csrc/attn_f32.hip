@@ -54,6 +54,7 @@ struct AttnArgs {
   unsigned upg, urem;
   float* ws;
   unsigned* counters;
+  int Sq;  // queries = token rows [0, Sq) (1 <= Sq <= S); keys / values = all S rows.  nq = query blocks of Sq
 };
 constexpr int SLAB_FLOATS = 66 * 256;  // [64 O values + m + l][256 threads of key group 0]
 
@@ -61,6 +62,19 @@ __device__ __forceinline__ unsigned range_start(unsigned g, const AttnArgs& p) {
 __device__ __forceinline__ unsigned range_of(unsigned x, const AttnArgs& p) {  // the range that holds tile-item x
   const unsigned big = p.urem * (p.upg + 1);
   return x < big ? x / (p.upg + 1) : p.urem + (x - big) / p.upg;
+}
+
+// The query count is needed before and after the key loop only: re-read from the kernarg segment where it is used, through a laundered
+// pointer, it is not one more scalar held across the loop (the balanced kernel already spills scalars; attn_split.hip's TAIL epilogue)
+__device__ __forceinline__ int fresh_Sq(const AttnArgs& p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const __attribute__((address_space(4))) AttnArgs* KArgs;
+  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  return ka->Sq;
+#else
+  return p.Sq;
+#endif
 }
 
 template <int NGRP, bool BAL = false>
@@ -116,7 +130,7 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_f32_ke
   float qf[16][4];
   {
     const int qrow = q0 + l31;
-    const bool ok = qrow < S;
+    const bool ok = qrow < fresh_Sq(p);  // (rows past the queries: zero fragments, never stored)
     const float* qp = Qg + static_cast<long long>(ok ? qrow : 0) * ld + 4 * half;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
@@ -376,7 +390,7 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_f32_ke
   // ---- normalise and store: lane holds O[q0+l31][32d + 8g + 4half + (0..3)] in o[d][4g..4g+3]
   auto store_rows = [&]() {
     const int qrow = q0 + l31;
-    if (qrow < S) {
+    if (qrow < fresh_Sq(p)) {
       const float inv = 1.0f / l_run;
       float* op = p.O + static_cast<long long>(b) * p.o_bs + static_cast<long long>(qrow) * p.ldo + head * HD + 4 * half;
 #pragma unroll
@@ -461,23 +475,26 @@ extern "C" long long ldc_attn_fwd_workspace_bytes(void) {
   return BAL_COUNTER_BYTES + 2LL * BAL_G * SLAB_FLOATS * static_cast<long long>(sizeof(float));
 }
 
-extern "C" int ldc_attn_fwd_ws(const float* Q, const float* K, const float* V, float* O, int B, int S, int H, int ld_qkv,
-                               long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace,
-                               long long workspace_bytes, void* stream) {
+// queries = the first Sq of the S token rows; units = query blocks of Sq x heads x batch, and everything chosen from the unit count (the
+// balanced cut and its ranges, the ticket counters, one or two wave groups) is chosen from that number.  Sq == S is ldc_attn_fwd_ws.
+extern "C" int ldc_attn_fwd_ws_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                                     long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace,
+                                     long long workspace_bytes, void* stream) {
   LDC_CHECK_PTR(Q);
   LDC_CHECK_PTR(K);
   LDC_CHECK_PTR(V);
   LDC_CHECK_PTR(O);
-  if (B <= 0 || S <= 0 || H <= 0) return LDC_ERR_ARG;
+  if (B <= 0 || S <= 0 || H <= 0 || Sq <= 0 || Sq > S) return LDC_ERR_ARG;
   LDC_CHECK_ALIGN16(Q);
   LDC_CHECK_ALIGN16(K);
   LDC_CHECK_ALIGN16(V);
   LDC_CHECK_ALIGN16(O);
   if ((ld_qkv & 3) || (ldo & 3) || (qkv_bs & 3) || (o_bs & 3)) return LDC_ERR_ALIGN;
-  if (static_cast<long long>(ldc_cdiv(S, QB)) * H * B > 0x7fffffffLL) return LDC_ERR_UNSUPPORTED;
+  if (static_cast<long long>(ldc_cdiv(Sq, QB)) * H * B > 0x7fffffffLL) return LDC_ERR_UNSUPPORTED;
   AttnArgs p{Q, K, V, O, S, H, ld_qkv, ldo, qkv_bs, o_bs,
              0.08838834764831845f * 1.4426950408889634f};  // 1/sqrt(128) * log2(e)
-  p.nq = ldc_cdiv(S, QB);
+  p.Sq = Sq;
+  p.nq = ldc_cdiv(Sq, QB);
   p.kbias = key_bias;
   p.nt = ldc_cdiv(S, KT);
   const long long units = static_cast<long long>(p.nq) * H * B;
@@ -523,7 +540,18 @@ extern "C" int ldc_attn_fwd_ws(const float* Q, const float* K, const float* V, f
   return ldc_launch_status();
 }
 
+extern "C" int ldc_attn_fwd_ws(const float* Q, const float* K, const float* V, float* O, int B, int S, int H, int ld_qkv,
+                               long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace,
+                               long long workspace_bytes, void* stream) {
+  return ldc_attn_fwd_ws_qrows(Q, K, V, O, B, S, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias, workspace, workspace_bytes, stream);
+}
+
 // without a workspace: the one-unit-per-workgroup grids
+extern "C" int ldc_attn_fwd_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H,
+                                  int ld_qkv, long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* stream) {
+  return ldc_attn_fwd_ws_qrows(Q, K, V, O, B, S, Sq, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias, nullptr, 0, stream);
+}
+
 extern "C" int ldc_attn_fwd(const float* Q, const float* K, const float* V, float* O, int B, int S, int H,
                             int ld_qkv, long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* stream) {
   return ldc_attn_fwd_ws(Q, K, V, O, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias, nullptr, 0, stream);

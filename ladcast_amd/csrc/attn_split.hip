@@ -166,6 +166,7 @@ struct AttnArgs {
   // are combined by attn_tail_merge_kernel
   int n_full, n_pieces, slices;
   float* part;
+  int Sq;  // queries = token rows [0, Sq) (1 <= Sq <= S); keys / values = all S rows.  nq = query blocks of Sq
 };
 constexpr int PART_FLOATS = 68 * 256;  // per piece: [64 O values + m0, m1, l0, l1][4 waves x 64 lanes]
 
@@ -235,11 +236,11 @@ __device__ __forceinline__ int fresh_lane() {
 // ---- epilogue: a lane owns query row 16 qt + c16 and, per d tile, the 4 consecutive columns 16 dt + 4 g4 .. + 3 ----
 __device__ __forceinline__ void attn_store_rows(const AttnArgs& p, int b, int head, int q0, int c16, int g4, const f32x4 (&o)[8][2],
                                                 const float (&l_run)[2]) {
-  const int S = p.S;
+  const int Sq = p.Sq;
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int qrow = q0 + 16 * qt + c16;
-    if (qrow >= S) continue;
+    if (qrow >= Sq) continue;
     const float inv = 1.0f / l_run[qt];
     float* orow = p.O + static_cast<long long>(b) * p.o_bs + static_cast<long long>(qrow) * p.ldo + head * HD;
 #pragma unroll
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(256) void attn_tail_merge_kernel(AttnArgs p) {
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int qrow = q0 + 16 * qt + c16;
-    if (qrow >= p.S) continue;  // (the 4 lanes of a row share qrow: the lane-group swap of the split format stays among active lanes)
+    if (qrow >= p.Sq) continue;  // (the 4 lanes of a row share qrow: the lane-group swap of the split format stays among active lanes)
     attn_store_tile(p, b, head, qrow, dt, g4, o[qt], l[qt]);
   }
 }
@@ -379,10 +380,19 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_split_
   // Q fragments (B operand): query 16 qt + c16, d = 32 s + 8 g4 + j <-> split group 4 s + g4
   bf16x8 qh[2][4], ql[2][4];
   const int lane_p = TAIL ? fresh_lane() : lane;
+  int Sq = p.Sq;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (TAIL) {  // used here and in the epilogue only: re-read from the kernarg segment, like the epilogue's arguments (see there)
+    typedef const __attribute__((address_space(4))) AttnArgs* KArgs;
+    KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    Sq = ka->Sq;
+  }
+#endif
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     int qrow = q0 + 16 * qt + (lane_p & 15);
-    qrow = qrow < S ? qrow : S - 1;  // rows past S: any valid row (never stored)
+    qrow = qrow < Sq ? qrow : Sq - 1;  // rows past the queries: any valid query row (never stored)
     const unsigned char* qp = p.Q + bh_off + static_cast<unsigned>(qrow) * ldb + 32 * (lane_p >> 4);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -659,7 +669,7 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_split_
       typedef const __attribute__((address_space(4))) AttnArgs* KArgs;
       KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
       asm volatile("" : "+s"(ka));
-      pe.O = ka->O; pe.S = ka->S; pe.ldo = ka->ldo; pe.o_bs = ka->o_bs; pe.out_split = ka->out_split; pe.part = ka->part;
+      pe.O = ka->O; pe.Sq = ka->Sq; pe.ldo = ka->ldo; pe.o_bs = ka->o_bs; pe.out_split = ka->out_split; pe.part = ka->part;
     }
 #endif
     const AttnArgs& p = pe;
@@ -732,12 +742,13 @@ static bool attn_tail_plan(long long nwg, int nt, int* n_full, int* n_pieces, in
   return true;
 }
 
-extern "C" long long ldc_attn_fwd_split_workspace_bytes(int B, int S, int H) {
-  if (B <= 0 || S <= 0 || H <= 0) return 0;
+extern "C" long long ldc_attn_fwd_split_qrows_workspace_bytes(int B, int S, int Sq, int H) {
+  if (B <= 0 || S <= 0 || H <= 0 || Sq <= 0 || Sq > S) return 0;
   int nf, np, sl;
-  if (!attn_tail_plan(static_cast<long long>(ldc_cdiv(S, QB)) * H * B, ldc_cdiv(S, KT), &nf, &np, &sl)) return 0;
+  if (!attn_tail_plan(static_cast<long long>(ldc_cdiv(Sq, QB)) * H * B, ldc_cdiv(S, KT), &nf, &np, &sl)) return 0;
   return static_cast<long long>(np) * PART_FLOATS * static_cast<long long>(sizeof(float));
 }
+extern "C" long long ldc_attn_fwd_split_workspace_bytes(int B, int S, int H) { return ldc_attn_fwd_split_qrows_workspace_bytes(B, S, S, H); }
 
 // the most any call shape can ask for (attn_tail_plan: rem <= 128 left-over units x floor(256 / rem) slices <= 256 pieces): what a caller
 // that captures launches into graphs allocates ONCE, so that no later shape ever makes it replace a pointer a captured launch holds
@@ -745,14 +756,16 @@ extern "C" long long ldc_attn_fwd_split_workspace_max_bytes(void) {
   return 256LL * PART_FLOATS * static_cast<long long>(sizeof(float));
 }
 
-extern "C" int ldc_attn_fwd_split(const float* Q, const float* K, const float* V, float* O, int B, int S, int H, int ld_qkv,
-                                  long long qkv_bs, int ldo, long long o_bs, const float* key_bias, int flags, void* workspace,
-                                  long long workspace_bytes, void* stream) {
+// queries = the first Sq of the S token rows; units = query blocks of Sq x heads x batch, and the choices made from the unit count (one
+// or two wave groups, the persistent form with its key-sliced tail and merge) are made from that number.  Sq == S is ldc_attn_fwd_split.
+extern "C" int ldc_attn_fwd_split_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                                        long long qkv_bs, int ldo, long long o_bs, const float* key_bias, int flags, void* workspace,
+                                        long long workspace_bytes, void* stream) {
   LDC_CHECK_PTR(Q);
   LDC_CHECK_PTR(K);
   LDC_CHECK_PTR(V);
   LDC_CHECK_PTR(O);
-  if (B <= 0 || S <= 0 || H <= 0) return LDC_ERR_ARG;
+  if (B <= 0 || S <= 0 || H <= 0 || Sq <= 0 || Sq > S) return LDC_ERR_ARG;
   LDC_CHECK_ALIGN16(Q);
   LDC_CHECK_ALIGN16(K);
   LDC_CHECK_ALIGN16(V);
@@ -762,19 +775,19 @@ extern "C" int ldc_attn_fwd_split(const float* Q, const float* K, const float* V
   const int out_split = (flags & LDC_ATTN_OUT_BF16) ? LDC_FMT_BF16 : (flags & LDC_ATTN_OUT_SPLIT) ? LDC_FMT_SPLIT : 0;
   const bool one_term = (flags & LDC_ATTN_BF16_1TERM) != 0;
   if (out_split && ((ldo & 7) || (o_bs & 7) || (reinterpret_cast<unsigned long long>(O) & 31ull))) return LDC_ERR_ALIGN;
-  if (static_cast<long long>(ldc_cdiv(S, QB)) * H * B > 0x7fffffffLL) return LDC_ERR_UNSUPPORTED;
+  if (static_cast<long long>(ldc_cdiv(Sq, QB)) * H * B > 0x7fffffffLL) return LDC_ERR_UNSUPPORTED;
   if (static_cast<long long>(S) * ld_qkv * 4 >= (1LL << 32)) return LDC_ERR_UNSUPPORTED;  // 32-bit row offsets inside one batch entry
   AttnArgs p{};
   p.Q = reinterpret_cast<const unsigned char*>(Q);
   p.K = reinterpret_cast<const unsigned char*>(K);
   p.V = reinterpret_cast<const unsigned char*>(V);
   p.O = O;
-  p.S = S; p.H = H; p.ldo = ldo; p.o_bs = o_bs;
+  p.S = S; p.Sq = Sq; p.H = H; p.ldo = ldo; p.o_bs = o_bs;
   p.ldb = static_cast<long long>(ld_qkv) * 4;
   p.bsb = qkv_bs * 4;
   p.out_split = out_split;
   p.nt = ldc_cdiv(S, KT);
-  p.nq = ldc_cdiv(S, QB);
+  p.nq = ldc_cdiv(Sq, QB);
   dim3 grid(static_cast<unsigned>(p.nq) * H * B);
   p.kbias = key_bias;
   const long long nwg = static_cast<long long>(p.nq) * H * B;
@@ -831,4 +844,10 @@ extern "C" int ldc_attn_fwd_split(const float* Q, const float* K, const float* V
   }
 #undef LDC_ATTN_LAUNCH
   return ldc_launch_status();
+}
+
+extern "C" int ldc_attn_fwd_split(const float* Q, const float* K, const float* V, float* O, int B, int S, int H, int ld_qkv,
+                                  long long qkv_bs, int ldo, long long o_bs, const float* key_bias, int flags, void* workspace,
+                                  long long workspace_bytes, void* stream) {
+  return ldc_attn_fwd_split_qrows(Q, K, V, O, B, S, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias, flags, workspace, workspace_bytes, stream);
 }

@@ -78,6 +78,8 @@ def _load():
         "ldc_attn_fwd_split_workspace_bytes": (L, [I, I, I]),
         "ldc_attn_fwd_split_workspace_max_bytes": (L, []),
         "ldc_attn_fwd_split": (I, [P, P, P, P, I, I, I, I, L, I, L, P, I, P, L, P]),
+        "ldc_attn_fwd_split_qrows_workspace_bytes": (L, [I, I, I, I]),
+        "ldc_attn_fwd_split_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, I, P, L, P]),
         "ldc_pack_weight_bf16x2": (I, [P, P, I, I, I, P]),
         "ldc_pack_weight_bf16": (I, [P, P, I, I, I, P]),
         "ldc_linear_small": (I, [P, I, P, P, P, I, P, I, I, I, I, I, P]),
@@ -86,6 +88,8 @@ def _load():
         "ldc_gate_residual_layernorm": (I, [P, P, P, P, I, I, I, I, L, I, L, I, I, L, P, P, F, I, P]),
         "ldc_attn_fwd": (I, [P, P, P, P, I, I, I, I, L, I, L, P, P]),
         "ldc_attn_fwd_ws": (I, [P, P, P, P, I, I, I, I, L, I, L, P, P, L, P]),
+        "ldc_attn_fwd_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P]),
+        "ldc_attn_fwd_ws_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P, L, P]),
         "ldc_attn_fwd_workspace_bytes": (L, []),
         "ldc_qk_rmsnorm_rope": (I, [P, P, I, I, I, I, I, L, P, P, F, P, P, P]),
         "ldc_sphere_conv_nhwc_split": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, L, P]),
@@ -306,20 +310,27 @@ def _attn_f32_workspace(device):
     return ws
 
 
-def attn_fwd(Q, K, V, O, *, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias=None, use_workspace=True):
+def attn_fwd(Q, K, V, O, *, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias=None, use_workspace=True, Sq=None):
     """exact-fp32 attention on fp32 q / k / v views (ldc_attn_fwd_ws); key_bias: [S] additive score bias per key (or None).
-    use_workspace=False: never the balanced schedule (ldc_attn_fwd; A/B, tests)"""
+    use_workspace=False: never the balanced schedule (ldc_attn_fwd; A/B, tests).  Sq: the queries are the first Sq token rows only
+    (keys / values: all S; rows >= Sq of O untouched; ldc_attn_fwd_qrows / _ws_qrows)"""
     _dev(Q, K, V, O, key_bias)
     if key_bias is not None and key_bias.numel() < S:
         raise ValueError("key_bias must hold one value per key")
     if not use_workspace:
-        _check(lib.ldc_attn_fwd(_p(Q), _p(K), _p(V), _p(O), B, S, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), _stream()), "ldc_attn_fwd")
+        if Sq is None:
+            _check(lib.ldc_attn_fwd(_p(Q), _p(K), _p(V), _p(O), B, S, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), _stream()), "ldc_attn_fwd")
+        else:
+            _check(lib.ldc_attn_fwd_qrows(_p(Q), _p(K), _p(V), _p(O), B, S, Sq, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), _stream()), "ldc_attn_fwd_qrows")
         return
     ws = _attn_f32_workspace(Q.device)
-    st = lib.ldc_attn_fwd_ws(_p(Q), _p(K), _p(V), _p(O), B, S, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), _p(ws), ws.numel() * 4, _stream())
+    if Sq is None:
+        st = lib.ldc_attn_fwd_ws(_p(Q), _p(K), _p(V), _p(O), B, S, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), _p(ws), ws.numel() * 4, _stream())
+    else:
+        st = lib.ldc_attn_fwd_ws_qrows(_p(Q), _p(K), _p(V), _p(O), B, S, Sq, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), _p(ws), ws.numel() * 4, _stream())
     if st != 0 and not torch.cuda.is_current_stream_capturing():
         ws.zero_()  # a launch that did not complete may leave ticket counters non-zero: re-arm them before anyone launches again
-    _check(st, "ldc_attn_fwd_ws")
+    _check(st, "ldc_attn_fwd_ws" if Sq is None else "ldc_attn_fwd_ws_qrows")
 
 
 def rearm_attention_workspaces(device=None):
@@ -458,17 +469,25 @@ def _attn_workspace(device, nbytes):
     return ws
 
 
-def attn_fwd_split(Q, K, V, O, *, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, out_split=False, one_term=False, key_bias=None, use_workspace=True):
+def attn_fwd_split(Q, K, V, O, *, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, out_split=False, one_term=False, key_bias=None, use_workspace=True, Sq=None):
     """attention on row-major split-bf16 operand rows (ldc_attn_fwd_split); key_bias: additive score bias per key, padded to a multiple
-    of 32 entries (`pad_key_bias`), or None.  use_workspace=False: never the TAIL schedule (A/B, tests)"""
+    of 32 entries (`pad_key_bias`), or None.  use_workspace=False: never the TAIL schedule (A/B, tests).  Sq: the queries are the first
+    Sq token rows only (keys / values: all S; rows >= Sq of O untouched; ldc_attn_fwd_split_qrows)"""
     _dev(Q, K, V, O, key_bias)
-    nbytes = lib.ldc_attn_fwd_split_workspace_bytes(B, S, H) if use_workspace else 0
+    if Sq is None:
+        nbytes = lib.ldc_attn_fwd_split_workspace_bytes(B, S, H) if use_workspace else 0
+    else:
+        nbytes = lib.ldc_attn_fwd_split_qrows_workspace_bytes(B, S, Sq, H) if use_workspace else 0
     ws = _attn_workspace(Q.device, nbytes) if nbytes > 0 else None
     if key_bias is not None and key_bias.numel() < 32 * ((S + 31) // 32):
         raise ValueError("key_bias must be padded to a multiple of 32 keys (hip.pad_key_bias)")
     flags = (ATTN_OUT_BF16 if int(out_split) == FMT_BF16 else ATTN_OUT_SPLIT if out_split else 0) | (ATTN_BF16_1TERM if one_term else 0)
-    _check(lib.ldc_attn_fwd_split(_p(Q), _p(K), _p(V), _p(O), B, S, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), flags, _p(ws), 0 if ws is None else ws.numel() * 4,
-                                  _stream()), "ldc_attn_fwd_split")
+    if Sq is None:
+        _check(lib.ldc_attn_fwd_split(_p(Q), _p(K), _p(V), _p(O), B, S, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), flags, _p(ws), 0 if ws is None else ws.numel() * 4,
+                                      _stream()), "ldc_attn_fwd_split")
+    else:
+        _check(lib.ldc_attn_fwd_split_qrows(_p(Q), _p(K), _p(V), _p(O), B, S, Sq, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), flags, _p(ws),
+                                            0 if ws is None else ws.numel() * 4, _stream()), "ldc_attn_fwd_split_qrows")
 
 
 def pad_key_bias(bias):

@@ -592,8 +592,9 @@ class LaDCastTransformer3DModel(ModelMixin):
         hip.linear_small(ws.p1, tx.linear_2.weight, out, rows=B, N=D, K=D, bias=tx.linear_2.bias, add=t2, add_rows=Bt, mod=te,
                          mod_rows=1 if te is None else te.shape[0])
 
-    def _attention(self, ws, B, row0, Sx, Sc, out, ldo, o_bs, seg_x, seg_c, out_split=False, key_bias=None, normed=False):
-        """Attention over token rows [row0, row0 + Sx + Sc) of the fused qkv buffer -> out.
+    def _attention(self, ws, B, row0, Sx, Sc, out, ldo, o_bs, seg_x, seg_c, out_split=False, key_bias=None, normed=False, Sq=None):
+        """Attention over token rows [row0, row0 + Sx + Sc) of the fused qkv buffer -> out.  Sq: only the first Sq of those rows are
+        queries (and rows of `out` that are written); all of them stay keys / values.
         fp32 mode: q/k RMSNorm + RoPE per segment in place (seg = (norm_q, norm_k, cos, sin): rows [row0, row0+Sx) use seg_x, the
         next Sc rows seg_c; ldc_qk_rmsnorm_rope) + ldc_attn_fwd.  Split-bf16 / bf16 modes: the QKV projection's epilogue has already
         written the normed, rotated, scaled and split operand rows (`_qkv_epi`), so this is ldc_attn_fwd_split alone."""
@@ -606,7 +607,7 @@ class LaDCastTransformer3DModel(ModelMixin):
         v = qkv[:, row0:, 2 * D : 3 * D]
         if self.gemm_precision in ("bf16x3", "bf16"):
             hip.attn_fwd_split(q, k, v, out, B=B, S=S, H=H, ld_qkv=3 * D, qkv_bs=full * 3 * D, ldo=ldo, o_bs=o_bs, out_split=out_split,
-                               one_term=self.gemm_precision == "bf16", key_bias=key_bias)
+                               one_term=self.gemm_precision == "bf16", key_bias=key_bias, Sq=Sq)
             return
         segs = [] if normed else [sg for sg in ((Sx, seg_x), (Sc, seg_c)) if sg[0] > 0]  # normed: the QKV projection's epilogue did it
         r0 = row0
@@ -614,7 +615,7 @@ class LaDCastTransformer3DModel(ModelMixin):
             hip.qk_rmsnorm_rope(qkv[:, :, 0:D], qkv[:, :, D : 2 * D], B=B, row0=r0, rows=rows, H=H, ld=3 * D, bs=full * 3 * D,
                                 wq=nq.weight, wk=nk.weight, eps=nq.eps, cos=c, sin=s_)
             r0 += rows
-        hip.attn_fwd(q, k, v, out, B=B, S=S, H=H, ld_qkv=3 * D, qkv_bs=full * 3 * D, ldo=ldo, o_bs=o_bs, key_bias=key_bias)
+        hip.attn_fwd(q, k, v, out, B=B, S=S, H=H, ld_qkv=3 * D, qkv_bs=full * 3 * D, ldo=ldo, o_bs=o_bs, key_bias=key_bias, Sq=Sq)
 
     def _qkv_epi(self, norm_q, norm_k, rope):
         """epilogue descriptor of a fused QKV projection (split modes): per-head RMSNorm weights + compact rotary table (None = no RoPE)"""
@@ -674,7 +675,7 @@ class LaDCastTransformer3DModel(ModelMixin):
             out = self._main_device(hidden_states, pack, idx)
             return (out,) if not return_dict else SimpleNamespace(sample=out)
         if self.use_hip_graph:
-            gkey = (B, Bt, C_in, R, T_in, Hh, Ww, None if te is None else (te.data_ptr(), te.shape[0]))
+            gkey = (B, Bt, C_in, R, T_in, Hh, Ww, None if te is None else (te.data_ptr(), te.shape[0]), bool(self.skip_unread_rows))
             ent = self._graphs.get(gkey)
             if ent is None:
                 sx, st, sk = torch.empty_like(hidden_states), torch.empty_like(timestep), torch.empty_like(conditioning_tensors)
@@ -744,6 +745,13 @@ class LaDCastTransformer3DModel(ModelMixin):
     # sampler chunks evaluate the conditioning path for all their noise levels at once unless this is switched off (A/B measurements,
     # `bench.py --no-batched-conditioning`); results agree to fp32 rounding (another stream-K cut of the same sums), not bit for bit
     batch_conditioning = True
+    # The output head reads the pred rows h_x only, so nothing reads the conditioning rows the LAST single-stream block writes: with this
+    # on, that block runs proj_mlp, the attention's queries and proj_out over the Nx pred rows alone (its QKV projection still covers all
+    # S rows: the conditioning rows' keys and values are needed).  The pred rows see the same operands; results agree to fp32 rounding
+    # (other tile / unit counts cut the same sums elsewhere), not bit for bit.  Off: every row, as the reference computes it (A/B
+    # measurements).  Part of the key of every cached graph, here and in the pipelines.  Blocks with a user-supplied attention processor
+    # and models without single blocks compute every row either way.
+    skip_unread_rows = True
     COND_MAX_ROWS = 96  # (noise level, member) entries per conditioning pass: bounds its workspace (30 MB per entry at 375M)
 
     @torch.no_grad()
@@ -1026,8 +1034,11 @@ class LaDCastTransformer3DModel(ModelMixin):
             run(down)
 
         # 5. single-stream blocks, models/LaDCast_3D_model.py:426-468
-        for blk in self.single_transformer_blocks:
+        n_single = len(self.single_transformer_blocks)
+        for i_blk, blk in enumerate(self.single_transformer_blocks):
             pa = plan.attn[id(blk.attn)]
+            # rows of this block's proj_mlp, attention queries and proj_out: after the last block only h_x is read (`skip_unread_rows`)
+            Mq = Nx if (self.skip_unread_rows and i_blk == n_single - 1 and blk.attn.foreign_processor is None) else S
             mod = mod_of(blk.norm.linear, 3 * D)
             F = blk.proj_mlp.weight.shape[0]
             W5 = D + F
@@ -1042,13 +1053,13 @@ class LaDCastTransformer3DModel(ModelMixin):
                 ws.cat[:, Nx:, :D].copy_(ca)
             else:
                 nd = run_qkv([
-                    G(ws.nh, blk.proj_mlp.weight, cat_mlp, M=S, N=F, K=D, batch=B, a_bs=SD, ldc=W5, c_bs=S * W5, bias=blk.proj_mlp.bias, act=hip.ACT_GELU_TANH,
+                    G(ws.nh, blk.proj_mlp.weight, cat_mlp, M=Mq, N=F, K=D, batch=B, a_bs=SD, ldc=W5, c_bs=S * W5, bias=blk.proj_mlp.bias, act=hip.ACT_GELU_TANH,
                       flags=AS | CS),
                     G(ws.nh, pa.wqkv, ws.qkv, M=S, N=3 * D, K=D, batch=B, a_bs=SD, c_bs=S * 3 * D, bias=pa.bqkv, flags=AS),
                 ], [None, self._qkv_epi(blk.attn.norm_q, blk.attn.norm_k, jk)])
                 self._attention(ws, B, 0, Nx, Nc, ws.cat, W5, S * W5, (blk.attn.norm_q, blk.attn.norm_k, pc, ps),
-                                (blk.attn.norm_q, blk.attn.norm_k, cc, cs), out_split=fmt, key_bias=kb_all, normed=nd)
-            run1(ws.cat, blk.proj_out.weight, ws.h, M=S, N=D, K=W5, batch=B, a_bs=S * W5, c_bs=SD, bias=blk.proj_out.bias,
+                                (blk.attn.norm_q, blk.attn.norm_k, cc, cs), out_split=fmt, key_bias=kb_all, normed=nd, Sq=None if Mq == S else Mq)
+            run1(ws.cat, blk.proj_out.weight, ws.h, M=Mq, N=D, K=W5, batch=B, a_bs=S * W5, c_bs=SD, bias=blk.proj_out.bias,
                         gate=mod[:, 2 * D :], gate_bs=NM, R=ws.h, ldr=D, r_bs=SD, flags=AS)
 
         # 6. output head, models/LaDCast_3D_model.py:1044-1062 (patch size 1: un-patchify == transpose)

@@ -79,7 +79,8 @@ def edm_AR_sampler(
         te = net.time_elapsed_embedding(timestamps)  # eager, cached per chunk; the graph reads its persistent buffer
         plan_id = net.plan_identity()  # a re-packed / re-loaded model gets new graphs
         key = (tuple(shape), tuple(known.shape), num_inference_steps, tuple(float(v) for v in t_steps.tolist()),
-               None if te is None else (te.data_ptr(), tuple(te.shape)), str(device), plan_id, batched)
+               None if te is None else (te.data_ptr(), tuple(te.shape)), str(device), plan_id, batched,
+               bool(getattr(net, "skip_unread_rows", False)))  # (the graph bakes in which rows the last single block computes)
         prepare = net.prepare_conditioning if batched else None
         key = ("edm_chunk",) + key
         cache = net._graphs  # the model's graph store: dropped with the packed weights (load_state_dict, .to(), precision switch)

@@ -107,7 +107,7 @@ class AutoRegressive2DPipeline:
         te = net.time_elapsed_embedding(timestamps)
         key = (tuple(image.shape), tuple(known.shape), num_inference_steps, sch.graph_signature(),
                tuple(sorted((k, str(v)) for k, v in self.scheduler_step_kwargs.items())), None if te is None else (te.data_ptr(), tuple(te.shape)), str(dev), net.plan_identity(),
-               bool(getattr(net, "batch_conditioning", False)))
+               bool(getattr(net, "batch_conditioning", False)), bool(getattr(net, "skip_unread_rows", False)))
         key = ("pipeline_loop",) + key
         cache = net._graphs  # the model's graph store: dropped with the packed weights (load_state_dict, .to(), precision switch)
         ent = cache.get(key)  # (one instance: the two-instance scheme of edm_sampler.py is not applied to this secondary loop)
