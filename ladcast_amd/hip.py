@@ -195,17 +195,37 @@ def gemm(A, W, C, *, M, N, K, batch=1, lda=None, ldw=None, ldc=None, a_bs=0, c_b
     _check(lib.ldc_gemm_bias_act(_p(A), _p(W), _p(bias), _p(gate), _p(R), _p(C), ctypes.byref(d), _stream()), "ldc_gemm_bias_act")
 
 
-_grouped_ws = {}
+_workspaces = {}  # (name, device, stream) -> fp32 tensor: every per-stream workspace of the library
+_outgrown = []  # replaced blocks of a growing workspace: a captured hipGraph may still point at the smaller one
+
+
+def _workspace(name, device, nbytes, init=None, grow=False):
+    """The workspace `name` of the current stream of `device`, created at the first call: at least `nbytes` bytes, initialised by `init`
+    (None: nothing | "zero": zero-filled | "grouped": ldc_gemm_grouped_workspace_init).  One per (device, stream): two streams never
+    share one.  A fixed workspace (grow=False) is allocated ONCE and never replaced: its pointer is baked into every hipGraph captured
+    on that stream, and graphs of several shapes stay alive side by side.  A first call inside a capture would take the block from the
+    graph's private pool and publish it to eager callers, and put its initialisation into the graph: refused - whoever captures warms
+    up on the capture stream first (`graphs.capture`).  A growing one (the scoring scratch) is replaced by a larger block when a call
+    asks for more; the smaller block stays alive."""
+    key = (name, str(device), torch.cuda.current_stream(device).cuda_stream)
+    ws = _workspaces.get(key)
+    if ws is None or (grow and ws.numel() * 4 < nbytes):
+        if not grow and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{name}: the first call on a stream must be made outside a graph capture (run one warm-up forward)")
+        if ws is not None:
+            _outgrown.append(ws)
+        ws = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+        if init == "zero":
+            ws.zero_()
+        elif init == "grouped":
+            _check(lib.ldc_gemm_grouped_workspace_init(c_void_p(ws.data_ptr()), ws.numel() * 4, _stream()), "ldc_gemm_grouped_workspace_init")
+        _workspaces[key] = ws
+    return ws
 
 
 def _grouped_workspace(device):
-    key = str(device)
-    key = (key, torch.cuda.current_stream(device).cuda_stream)  # one workspace per (device, stream)
-    if key not in _grouped_ws:
-        ws = torch.empty(lib.ldc_gemm_grouped_workspace_bytes() // 4, device=device, dtype=torch.float32)
-        _check(lib.ldc_gemm_grouped_workspace_init(c_void_p(ws.data_ptr()), ws.numel() * 4, _stream()), "ldc_gemm_grouped_workspace_init")
-        _grouped_ws[key] = ws
-    return _grouped_ws[key]
+    """stream-K tile counters (first MiB, zeroed once; every launch re-arms them) + partial-tile slabs of every grouped GEMM and conv"""
+    return _workspace("gemm_grouped", device, lib.ldc_gemm_grouped_workspace_bytes(), init="grouped")
 
 
 def gemm_problem(A, W, C, *, M, N, K, batch=1, lda=None, ldw=None, ldc=None, a_bs=0, c_bs=0, bias=None, gate=None, gate_bs=0, R=None,
@@ -293,21 +313,10 @@ def linear_small_grouped(problems):
     _check(lib.ldc_linear_small_grouped(arr, n, _stream()), "ldc_linear_small_grouped")
 
 
-_attn_f32_ws = {}
-
-
 def _attn_f32_workspace(device):
-    """counters + slabs of the exact-fp32 attention's balanced schedule (ldc_attn_fwd_ws), one per (device, stream), zero-filled once
-    (the launches leave the counters zero) and never replaced: captured hipGraphs hold its pointer.  As `_attn_workspace`: the first
-    call on a stream must be made outside a capture."""
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    ws = _attn_f32_ws.get(key)
-    if ws is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("attn_fwd: the first call on a stream must be made outside a graph capture (run one warm-up forward)")
-        ws = torch.zeros((lib.ldc_attn_fwd_workspace_bytes() + 3) // 4, device=device, dtype=torch.float32)
-        _attn_f32_ws[key] = ws
-    return ws
+    """counters + slabs of the exact-fp32 attention's balanced schedule (ldc_attn_fwd_ws), zero-filled once (the launches leave the
+    counters zero)"""
+    return _workspace("attn_fwd", device, lib.ldc_attn_fwd_workspace_bytes(), init="zero")
 
 
 def attn_fwd(Q, K, V, O, *, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias=None, use_workspace=True, Sq=None):
@@ -339,26 +348,16 @@ def rearm_attention_workspaces(device=None):
     hipGraph.  Must not be called while a graph that uses the workspace is running.  One workspace serves ONE stream: a graph captured on
     stream A and replayed on stream B shares A's counters - replay it on A, or give B its own capture."""
     want = None if device is None else torch.device(device).index
-    for ws in _attn_f32_ws.values():
-        if want is None or ws.device.index == want:
+    for key, ws in _workspaces.items():
+        if key[0] == "attn_fwd" and (want is None or ws.device.index == want):
             ws.zero_()
-
-
-_score_ws = {}
-_score_keep = []
 
 
 def ensemble_scores(forecast, truth, clim, lat_weight, out, *, M, C, H, W, member_stride, channel_stride, truth_channel_stride,
                     clim_channel_stride=0, nan_channel=-1, skill_map=None, spread_map=None):
     """out: [5][C] = acc, mse, crps_spread, crps_skill, crps (ladcast_hip.h: ldc_ensemble_scores)"""
     _dev(forecast, truth, clim, lat_weight, out, skill_map, spread_map)
-    need = int(lib.ldc_ensemble_scores_workspace_bytes(C, H, W))
-    key = (str(forecast.device), torch.cuda.current_stream(forecast.device).cuda_stream)
-    if key not in _score_ws or _score_ws[key].numel() * 4 < need:
-        if key in _score_ws:
-            _score_keep.append(_score_ws[key])  # a captured hipGraph may still point at the smaller one (as _rla_keep)
-        _score_ws[key] = torch.empty(need // 4 + 1, device=forecast.device, dtype=torch.float32)
-    ws = _score_ws[key]
+    ws = _workspace("ensemble_scores", forecast.device, int(lib.ldc_ensemble_scores_workspace_bytes(C, H, W)), grow=True)
     _check(lib.ldc_ensemble_scores(_p(forecast), member_stride, channel_stride, _p(truth), truth_channel_stride, _p(clim),
                                    clim_channel_stride, _p(lat_weight), M, C, H, W, nan_channel, _p(out), _p(skill_map), _p(spread_map),
                                    _p(ws), ws.numel() * 4, _stream()), "ldc_ensemble_scores")
@@ -448,22 +447,11 @@ def attn_qkv_prepare_split(Q, K, V, *, B, S, H, ld_qkv, qkv_bs, split_row, seg0=
                                           _p(seg1[0]), _p(seg1[1]), _p(seg1[2]), _p(seg1[3]), eps, _stream()), "ldc_attn_qkv_prepare_split")
 
 
-_attn_ws = {}
-
-
 def _attn_workspace(device, nbytes):
-    """scratch of the attention's TAIL schedule (more units than CUs), one per (device, stream), allocated ONCE at the largest size any call
-    shape can ask for (ldc_attn_fwd_split_workspace_max_bytes, 17.8 MB) and never replaced: its pointer is baked into every hipGraph
-    captured on that stream, and graphs of several batch sizes stay alive side by side (a regrown workspace would leave the older graphs
-    writing their partials into freed memory).  A first call inside a capture would take the block from the graph's private pool and
-    publish it to eager callers: refused - samplers warm up on their capture stream first, like the GEMM workspace."""
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    ws = _attn_ws.get(key)
-    if ws is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("attn_fwd_split: the first call on a stream must be made outside a graph capture (run one warm-up forward)")
-        ws = torch.empty((lib.ldc_attn_fwd_split_workspace_max_bytes() + 3) // 4, device=device, dtype=torch.float32)
-        _attn_ws[key] = ws
+    """scratch of the attention's TAIL schedule (more units than CUs), allocated at the largest size any call shape can ask for
+    (ldc_attn_fwd_split_workspace_max_bytes, 17.8 MB): a regrown workspace would leave the older graphs writing their partials into
+    freed memory"""
+    ws = _workspace("attn_fwd_split", device, lib.ldc_attn_fwd_split_workspace_max_bytes())
     if ws.numel() * 4 < nbytes:
         raise RuntimeError(f"attn_fwd_split: call shape asks for {nbytes} workspace bytes, more than ldc_attn_fwd_split_workspace_max_bytes")
     return ws

@@ -20,7 +20,7 @@ from typing import Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from .. import hip
+from .. import graphs, hip
 from .modeling_utils import ModelMixin
 from .sphere_conv import (SphereConv2d, ceil4, pack_dense_weight, pack_dense_weight_bf16, pack_dense_weight_bf16x3, pack_dense_weight_f32ring,
                           pack_depthwise_weight)
@@ -303,8 +303,23 @@ class AutoencoderDC(ModelMixin):
             raise NotImplementedError(self._FOREIGN_NOT_CAPTURABLE)
         self.use_hip_graph = bool(flag)
         if not flag:
-            self._graphs = {}
+            self._drop_graphs()
         return self
+
+    def _drop_graphs(self):
+        self._graphs = {}
+
+    def _drop_plan(self):
+        """the packed weights (rebuilt at the next call) and the graphs that hold raw pointers into them"""
+        self._plan = None
+        self._drop_graphs()
+
+    def capture_stream(self):
+        """the ONE side stream every graph of this model is captured on (per-stream workspaces are keyed by stream: one stream = one
+        set, however many graphs are captured)"""
+        if self._capture_stream is None:
+            self._capture_stream = torch.cuda.Stream(device=self.device)
+        return self._capture_stream
 
     _FOREIGN_NOT_CAPTURABLE = "a user-supplied DCAE attention processor runs eagerly (torch tensors): it cannot be captured into a hipGraph"
 
@@ -316,32 +331,13 @@ class AutoencoderDC(ModelMixin):
         if self._has_foreign_processor():
             # a processor installed after the capture (a plain attribute: nothing tells the model) - a cached graph would replay the
             # fused path and ignore it.  Checked here, before any capture or replay starts.
-            self._graphs = {}
+            self._drop_graphs()
             raise NotImplementedError(self._FOREIGN_NOT_CAPTURABLE)
         key = key + (self._plan_gen, self.gemm_precision)  # generation counter, not id(): a rebuilt dict may reuse a freed id
         ent = self._graphs.get(key)
         if ent is None:
-            dev = self.device
-            if self._capture_stream is None:
-                self._capture_stream = torch.cuda.Stream(device=dev)
-            side = self._capture_stream
-            st = [torch.empty_like(t) for t in inputs]
-            for a, b in zip(st, inputs):
-                a.copy_(b)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):  # warm-up on the capture stream: per-stream workspaces are created here
-                fn(*st)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                out = fn(*st)
-            ent = (graph, st, out)
-            self._graphs[key] = ent
-        graph, st, out = ent
-        for a, b in zip(st, inputs):
-            a.copy_(b)
-        graph.replay()
-        return out.clone()
+            ent = self._graphs[key] = graphs.capture(fn, inputs, self.device, self.capture_stream())
+        return ent.replay(*inputs)
 
     def set_gemm_precision(self, precision: str):
         """'fp32' (default): every conv on the exact-fp32 matrix cores; 'bf16x3': the dense 3x3 SphereConv2d layers, the 1x1 convs and
@@ -354,8 +350,7 @@ class AutoencoderDC(ModelMixin):
             raise ValueError("gemm precision must be 'fp32', 'bf16x3' or 'bf16'")
         if precision != self.gemm_precision:
             self.gemm_precision = precision
-            self._plan = None
-            self._graphs = {}  # captured graphs hold raw pointers into the old packed weights
+            self._drop_plan()
         return self
 
     def enable_tiling(self, *a, **k):
@@ -371,13 +366,11 @@ class AutoencoderDC(ModelMixin):
         self.use_slicing = False
 
     def _apply(self, fn, *a, **k):
-        self._plan = None
-        self._graphs = {}
+        self._drop_plan()
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
-        self._plan = None
-        self._graphs = {}
+        self._drop_plan()
         return super().load_state_dict(*a, **k)
 
     # -- plan: repacked weights (NHWC / tap-major) ------------------------------------------------

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import hip
+from .. import graphs, hip
 from .embeddings import get_year_sincos_embedding, rope_tables_from_grid, rotary_1d
 from .modeling_utils import ModelMixin
 
@@ -315,14 +315,27 @@ class LaDCastTransformer3DModel(ModelMixin):
             raise NotImplementedError("hipGraph capture is for the built-in attention path; a user-supplied attention processor runs eagerly")
         self.use_hip_graph = bool(flag)
         if not flag:
-            self._graphs = {}
+            self._drop_graphs()
         return self
+
+    def _drop_graphs(self):
+        """captured graphs hold raw pointers into the packed weights, the workspaces and the tables they were captured with"""
+        self._graphs = {}
+
+    def _drop_plan(self, device_caches=False):
+        """the packed weights (rebuilt at the next call; `plan_identity` changes) and the graphs that read them; device_caches (the
+        module moved): also every workspace and table made on the old device"""
+        self._plan = None
+        self._drop_graphs()
+        if device_caches:
+            self._ws, self._rope, self._te_buf, self._kbias = {}, {}, {}, {}
+            self._te_cache = None
 
     def set_attn_lat_weights(self, weights: torch.Tensor):
         """replace `attn_lat_weights` ((1, 1, 1, h * w) or (h * w,)) and drop the device copies / graphs made from the old ones"""
         self.attn_lat_weights = weights.detach().float().reshape(1, 1, 1, -1).cpu()
         self._kbias = {}
-        self._graphs = {}
+        self._drop_graphs()
         return self
 
     def _key_bias(self, frames, dev):
@@ -353,8 +366,7 @@ class LaDCastTransformer3DModel(ModelMixin):
             raise ValueError("gemm precision must be 'fp32', 'bf16x3' or 'bf16'")
         if mode != self.gemm_precision:
             self.gemm_precision = mode
-            self._plan = None
-            self._graphs = {}
+            self._drop_plan()
         return self
 
     # -- diffusers-style processor surface (models/LaDCast_3D_model.py:763-827) --------------
@@ -390,7 +402,7 @@ class LaDCastTransformer3DModel(ModelMixin):
         if self._foreign_processors():
             if self.use_hip_graph:
                 self.enable_hip_graph(False)  # captured graphs hold the fused path
-            self._graphs = {}
+            self._drop_graphs()
 
     def _foreign_processors(self):
         return [m for m in self.modules() if isinstance(m, _AttentionP) and m.foreign_processor is not None]
@@ -412,18 +424,11 @@ class LaDCastTransformer3DModel(ModelMixin):
 
     # -- plan: fused weights ---------------------------------------------------------------
     def _apply(self, fn, *a, **k):  # any .to()/.cuda() invalidates the fused copies + caches
-        self._plan = None
-        self._ws = {}
-        self._rope = {}
-        self._te_cache = None
-        self._te_buf = {}
-        self._graphs = {}
-        self._kbias = {}
+        self._drop_plan(device_caches=True)
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
-        self._plan = None
-        self._graphs = {}
+        self._drop_plan()
         return super().load_state_dict(*a, **k)
 
     @staticmethod
@@ -676,30 +681,11 @@ class LaDCastTransformer3DModel(ModelMixin):
             return (out,) if not return_dict else SimpleNamespace(sample=out)
         if self.use_hip_graph:
             gkey = (B, Bt, C_in, R, T_in, Hh, Ww, None if te is None else (te.data_ptr(), te.shape[0]), bool(self.skip_unread_rows))
+            inputs = [hidden_states, timestep, conditioning_tensors]
             ent = self._graphs.get(gkey)
             if ent is None:
-                sx, st, sk = torch.empty_like(hidden_states), torch.empty_like(timestep), torch.empty_like(conditioning_tensors)
-                sx.copy_(hidden_states)
-                st.copy_(timestep)
-                sk.copy_(conditioning_tensors)
-                # warm-up and capture on ONE side stream: per-stream workspaces (stream-K counters, attention operands)
-                # are created and initialised by the warm-up, so no allocation / memset ends up inside the graph
-                self.capture_stream().wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(self._capture_stream):
-                    self._forward_device(sx, st, sk, te)
-                torch.cuda.synchronize()
-                hip.rearm_attention_workspaces(dev)  # ticket counters of the balanced fp32 attention: zeroed before a (re)capture, with nothing in flight (hip.py)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, stream=self._capture_stream, capture_error_mode="thread_local"):
-                    sout = self._forward_device(sx, st, sk, te)
-                ent = (graph, sx, st, sk, sout)
-                self._graphs[gkey] = ent
-            graph, sx, st, sk, sout = ent
-            sx.copy_(hidden_states)
-            st.copy_(timestep)
-            sk.copy_(conditioning_tensors)
-            graph.replay()
-            out = sout.clone()
+                ent = self._graphs[gkey] = graphs.capture(lambda x, t, k: self._forward_device(x, t, k, te), inputs, dev, self.capture_stream())
+            out = ent.replay(*inputs)
         else:
             out = self._forward_device(hidden_states, timestep, conditioning_tensors, te)
         if not return_dict:

@@ -15,7 +15,7 @@ from typing import List, Optional, Union
 import numpy as np
 import torch
 
-from .. import hip
+from .. import graphs, hip
 from .torch_utils import randn_tensor
 
 
@@ -92,30 +92,18 @@ def edm_AR_sampler(
         cache[key + ("turn",)] = turn ^ 1
 
         def capture():
-            st_lat, st_known, st_out = torch.empty_like(latents), torch.empty_like(known), torch.empty(shape, device=device, dtype=torch.float32)
-            st_lat.copy_(latents)
-            st_known.copy_(known)
-            cn = c_noise_host.to(device)
-            side = net.capture_stream() if hasattr(net, "capture_stream") else torch.cuda.Stream(device=device)
-            side.wait_stream(torch.cuda.current_stream(device))
-            with torch.cuda.stream(side):  # warm-up on the capture stream: per-stream workspaces are created here
-                _heun_chunk(net.forward_launch_only, noise_scheduler, t_steps, cn, st_lat, st_known, te, st_out, shape, device, num_inference_steps, prepare)
-            torch.cuda.synchronize()
-            hip.rearm_attention_workspaces(device)  # ticket counters of the balanced fp32 attention: zeroed before a (re)capture, with nothing in flight (hip.py)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):  # other threads (the RCCL watchdog) may touch the runtime
-                _heun_chunk(net.forward_launch_only, noise_scheduler, t_steps, cn, st_lat, st_known, te, st_out, shape, device, num_inference_steps, prepare)
-            return (graph, st_lat, st_known, st_out, cn, side)
+            st_out, cn = torch.empty(shape, device=device, dtype=torch.float32), c_noise_host.to(device)
+
+            def chunk(lat, kn):
+                _heun_chunk(net.forward_launch_only, noise_scheduler, t_steps, cn, lat, kn, te, st_out, shape, device, num_inference_steps, prepare)
+                return st_out
+
+            return graphs.capture(chunk, [latents, known], device, net.capture_stream(), keep=cn)
 
         for inst in (turn, turn ^ 1):
             if cache.get(key + (inst,)) is None:
                 cache[key + (inst,)] = capture()
-        ent = cache[key + (turn,)]
-        graph, st_lat, st_known, st_out = ent[:4]
-        st_lat.copy_(latents)
-        st_known.copy_(known)
-        graph.replay()
-        return st_out.clone()
+        return cache[key + (turn,)].replay(latents, known)
 
     out = torch.empty(shape, device=device, dtype=torch.float32)
     c_noise = hip.upload_nonblocking(c_noise_host, device)

@@ -8,6 +8,7 @@ from typing import List, Optional, Tuple, Union
 
 import torch
 
+from .. import graphs
 from .torch_utils import randn_tensor
 from .utils import Fields2DPipelineOutput
 
@@ -111,40 +112,27 @@ class AutoRegressive2DPipeline:
         key = ("pipeline_loop",) + key
         cache = net._graphs  # the model's graph store: dropped with the packed weights (load_state_dict, .to(), precision switch)
         ent = cache.get(key)  # (one instance: the two-instance scheme of edm_sampler.py is not applied to this secondary loop)
-
-        # device copy of the timesteps for `prepare_conditioning`, made outside the capture (a host-to-device copy) and kept alive with
-        # the graph that reads it
-        ts_dev = sch.timesteps.to(device=dev, dtype=torch.float32).contiguous() if ent is None else None
-
-        def loop(img, kn, tsteps):
-            kb = kn if kn.shape[0] == batch_size else kn.expand(batch_size, *kn.shape[1:]).contiguous()
-            pack = net.prepare_conditioning(ts_dev, kb, te) if getattr(net, "batch_conditioning", False) else None
-            for i, (t, t_dev) in enumerate(zip(sch.timesteps, tsteps)):
-                x_in = sch.scale_model_input(img, t)
-                out = net.forward_launch_only(x_in, t_dev, kb, te, None if pack is None else (pack, i))
-                img = sch.step(out, t, img, **self.scheduler_step_kwargs, return_dict=False)[0]
-            return img
-
         if ent is None:
-            st_img, st_known = torch.empty_like(image), torch.empty_like(known)
-            st_img.copy_(image)
-            st_known.copy_(known)
+            # device copy of the timesteps for `prepare_conditioning`, made outside the capture (a host-to-device copy) and kept alive with
+            # the graph that reads it
+            ts_dev = sch.timesteps.to(device=dev, dtype=torch.float32).contiguous()
             # what the eager loop feeds the model, in the fp32 its forward() casts to (DDIM / DDPM timesteps are int64; the launch-only entry reads raw fp32)
             tsteps = [t.to(device=dev, dtype=torch.float32).expand(batch_size).contiguous() for t in sch.timesteps]
-            side = net.capture_stream() if hasattr(net, "capture_stream") else torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):  # warm-up on the capture stream (per-stream workspaces)
-                loop(st_img, st_known, tsteps)
-            torch.cuda.synchronize()
-            sch.set_timesteps(num_inference_steps)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                st_out = loop(st_img, st_known, tsteps)
-            ent = (graph, st_img, st_known, st_out, tsteps, side, sch.graph_state(), ts_dev)  # ts_dev: read by the graph
+
+            def loop(img, kn):
+                kb = kn if kn.shape[0] == batch_size else kn.expand(batch_size, *kn.shape[1:]).contiguous()
+                pack = net.prepare_conditioning(ts_dev, kb, te) if getattr(net, "batch_conditioning", False) else None
+                for i, (t, t_dev) in enumerate(zip(sch.timesteps, tsteps)):
+                    x_in = sch.scale_model_input(img, t)
+                    out = net.forward_launch_only(x_in, t_dev, kb, te, None if pack is None else (pack, i))
+                    img = sch.step(out, t, img, **self.scheduler_step_kwargs, return_dict=False)[0]
+                return img
+
+            # reset: the warm-up has advanced the scheduler's step index; the capture starts the loop anew
+            ent = graphs.capture(loop, [image, known], dev, net.capture_stream(), reset=lambda: sch.set_timesteps(num_inference_steps),
+                                 keep={"tsteps": tsteps, "ts_dev": ts_dev})
+            ent.keep["scheduler_state"] = sch.graph_state()  # the state the loop leaves the scheduler in: restored after every replay
             cache[key] = ent
-        graph, st_img, st_known, st_out = ent[:4]
-        st_img.copy_(image)
-        st_known.copy_(known)
-        graph.replay()
-        sch.set_graph_state(ent[6])
-        return st_out.clone()
+        out = ent.replay(image, known)
+        sch.set_graph_state(ent.keep["scheduler_state"])
+        return out
