@@ -564,6 +564,37 @@ int ldc_track_local_min(const float* fields, long long field_stride, const int* 
                         const double* lon, int W, const double* lat0, const double* lon0, const int* inner, int n_queries,
                         int* found, double* out_lat, double* out_lon, float* out_val, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * DC-AE reconstruction evaluation (recon.hip; reference ladcast/evaluate/evaluate_encdec_model.py).  Additive: ABI 5.
+ * Preprocessing of a raw batch, weather_dataset_preprocess_batch (dataloader/weather_dataset.py:203-224), in one pass:
+ *   out[b][c][h][w] = (x[b*batch_stride + c*channel_stride + h*row_stride + w] - mean[c]) / std_[c], b < B, c < C, h < H, w < W -
+ *   a real subtraction and a correctly rounded division, bit-equal to torch.  crop_south_pole is the caller's row offset into x,
+ *   incl_sur_pressure=False a C one smaller than the frames hold: no copy.  out is contiguous (B, C, H, W).
+ *   In channel sst_channel a NaN result becomes -2 and nan_mask (B, H, W), uint8, records where (1 / 0, every point written);
+ *   sst_channel = -1: no channel is treated, nan_mask may be NULL and is not written.  mean / std_: device vectors [C].
+ *   16-byte loads and stores when W % 4 == 0 and x, out and the three strides keep 16-byte alignment; a scalar path otherwise. */
+int ldc_recon_preprocess(const float* x, long long batch_stride, long long channel_stride, long long row_stride, int B, int C,
+                         int H, int W, const float* mean, const float* std_, int sst_channel, float* out,
+                         unsigned char* nan_mask, void* stream);
+/* Scores of a reconstruction pred (B, Cp, H, W) against target (B, C, H, W) followed by the static channels static_
+ * (S planes per batch element, static_batch_stride elements apart - 0 broadcasts one set; S = 0: static_ may be NULL), Cp = C + S,
+ * all contiguous fp32.  Replaces process_tensor_for_loss (metric/utils.py:20-63), LpLoss.rel with a weight (metric/loss.py:73-102)
+ * and the un-normalise / mse_loss / latitude-weighted mean of evaluate_encdec_model.py:211-231.  With p and t forced to -2 where
+ * nan_mask (B, H, W; NULL = none) is set in channel sst_channel, w = lat_weight[h], mean / std_ device vectors [Cp]:
+ *   rel[b][c]      = sqrt(sum_hw (w (p - t))^2) / sqrt(sum_hw (w t)^2)     (the weight enters squared; a zero target plane gives
+ *                    inf, or NaN when the numerator is zero too - no clamp)
+ *   abs_norm[b][c] = the numerator of rel (optional, NULL = not written: LpLoss.abs)
+ *   lw_mse[c]      = mean_bhw w ((p std_[c] + mean[c]) - (t std_[c] + mean[c]))^2, every product and sum rounded on its own as
+ *                    torch's fp32 ops are (multiply, add, multiply, add, subtract, square, multiply); masked points count as zeros
+ * Point values are bit-equal to the reference's; sums are fp32 in a fixed order (two calls: same bits).  B * Cp <= 65535,
+ * B * H * W < 2^24 (LDC_ERR_UNSUPPORTED).  workspace: ldc_recon_scores_workspace_bytes(B, Cp, H, W) bytes, 16-byte aligned, no
+ * initialisation needed.  16-byte loads when W % 4 == 0 and the bases are aligned; a scalar path otherwise. */
+long long ldc_recon_scores_workspace_bytes(int B, int Cp, int H, int W);
+int ldc_recon_scores(const float* pred, const float* target, const float* static_, long long static_batch_stride,
+                     const unsigned char* nan_mask, const float* lat_weight, const float* mean, const float* std_, int B, int C,
+                     int S, int H, int W, int sst_channel, float* rel, float* abs_norm, float* lw_mse, void* workspace,
+                     long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,9 @@ def _load():
         "ldc_track_nanmean": (I, [P, L, I, L, P, P]),
         "ldc_track_storms": (I, [P, L, L, L, L, P, P, I, P, I, P, P, I, I, POINTER(c_int), I, I, P, P, P, P]),
         "ldc_track_local_min": (I, [P, L, P, P, I, P, I, P, P, P, I, P, P, P, P, P]),
+        "ldc_recon_preprocess": (I, [P, L, L, L, I, I, I, I, P, P, I, P, P, P]),
+        "ldc_recon_scores_workspace_bytes": (L, [I, I, I, I]),
+        "ldc_recon_scores": (I, [P, P, P, L, P, P, P, P, I, I, I, I, I, I, P, P, P, P, L, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -361,6 +364,23 @@ def ensemble_scores(forecast, truth, clim, lat_weight, out, *, M, C, H, W, membe
     _check(lib.ldc_ensemble_scores(_p(forecast), member_stride, channel_stride, _p(truth), truth_channel_stride, _p(clim),
                                    clim_channel_stride, _p(lat_weight), M, C, H, W, nan_channel, _p(out), _p(skill_map), _p(spread_map),
                                    _p(ws), ws.numel() * 4, _stream()), "ldc_ensemble_scores")
+
+
+def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):
+    """out (B, C, H, W) = (x - mean_c) / std_c of the strided raw frames x; channel `sst_channel`: NaN -> -2 and nan_mask (B, H, W)
+    uint8 records where (ladcast_hip.h: ldc_recon_preprocess)"""
+    _dev(x, mean, std, out, nan_mask)
+    _check(lib.ldc_recon_preprocess(_p(x), batch_stride, channel_stride, row_stride, B, C, H, W, _p(mean), _p(std), sst_channel, _p(out),
+                                    _p(nan_mask), _stream()), "ldc_recon_preprocess")
+
+
+def recon_scores(pred, target, static, nan_mask, lat_weight, mean, std, rel, lw_mse, *, B, C, S, H, W, static_batch_stride=0, sst_channel=-1,
+                 abs_norm=None):
+    """rel / abs_norm [B][C + S], lw_mse [C + S] of a reconstruction against target + static channels (ladcast_hip.h: ldc_recon_scores)"""
+    _dev(pred, target, static, nan_mask, lat_weight, mean, std, rel, lw_mse, abs_norm)
+    ws = _workspace("recon_scores", pred.device, int(lib.ldc_recon_scores_workspace_bytes(B, C + S, H, W)), grow=True)
+    _check(lib.ldc_recon_scores(_p(pred), _p(target), _p(static), static_batch_stride, _p(nan_mask), _p(lat_weight), _p(mean), _p(std), B, C, S,
+                                H, W, sst_channel, _p(rel), _p(abs_norm), _p(lw_mse), _p(ws), ws.numel() * 4, _stream()), "ldc_recon_scores")
 
 
 def compact_rope_table(cos, sin):
