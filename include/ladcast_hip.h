@@ -513,6 +513,32 @@ int ldc_ensemble_scores(const float* forecast, long long member_stride, long lon
                         long long clim_channel_stride, const float* lat_weight, int M, int C, int H, int W,
                         int nan_channel, float* out, float* skill_map, float* spread_map, void* workspace,
                         long long workspace_bytes, void* stream);
+/* Every lead time of a decode batch of a rollout in one launch (additive under ABI 5): the driver of
+ * ladcast/evaluate/evaluate_ens_gpu.py:268-425 scores each decoder output where it lies.  Same point body, arms (M <= 64) and reduction
+ * order as ldc_ensemble_scores: column l of `out` holds the bits ldc_ensemble_scores gives for lead time l.
+ *   forecast: value (member m, lead l, channel c, point p) at forecast[m*member_stride + l*lead_stride + c*channel_stride + p] (elements;
+ *     the H*W plane contiguous): the reference's (ens, C, T, H, W) array, or the decoder's frame-major output for a batch laid out
+ *     lead-major then member, (L*ens, C, H, W): lead_stride = ens*C*HW, member_stride = C*HW, channel_stride = HW.
+ *   mean / std_ [C] device vectors, target_std: the inverse normalisation of decode_latent_ens fused into the load - every forecast
+ *     value becomes (x / target_std) * std_[c] + mean[c], each operation rounded on its own in the order of ldc_chan_affine(inverse=1)
+ *     and ldc_track_gather (bit-equal to de-normalising first).  mean == NULL: the forecast is in physical units already.  Truth and
+ *     climatology are never transformed.
+ *   truth / clim: tables of planes with one slot per lead time.  Lead l, channel c reads the plane at
+ *     truth + truth_slot[l]*truth_slot_stride + c*truth_channel_stride (likewise clim; clim == NULL = no ACC).  truth_slot / clim_slot
+ *     are DEVICE int arrays [L]; their values are the caller's responsibility (not checked on the device).  A (C, T, H, W) tensor is
+ *     slot_stride = HW, channel_stride = T*HW, slots 0..L-1; a resident (N, C, H, W) table is slot_stride = C*HW, channel_stride = HW.
+ *   out [5][C][L_total] = ens_acc, ens_mse, crps_spread, crps_skill, crps; columns l_off .. l_off + L - 1 are written, the others are
+ *     left alone, so successive launches fill the five (C, total_num_steps) arrays of one initial time.  nan_channel as above.  No
+ *     point maps.
+ * LDC_ERR_ARG: a null or non-positive argument, a workspace smaller than ldc_rollout_scores_workspace_bytes(C, L, H, W), or
+ * l_off + L > L_total; LDC_ERR_UNSUPPORTED: M > 64, C > 65535 or L > 65535. */
+long long ldc_rollout_scores_workspace_bytes(int C, int L, int H, int W);
+int ldc_rollout_scores(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride,
+                       const float* mean, const float* std_, float target_std, const float* truth, long long truth_slot_stride,
+                       long long truth_channel_stride, const int* truth_slot, const float* clim, long long clim_slot_stride,
+                       long long clim_channel_stride, const int* clim_slot, const float* lat_weight, int M, int C, int L, int H,
+                       int W, int nan_channel, float* out, int L_total, int l_off, void* workspace, long long workspace_bytes,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

@@ -13,6 +13,10 @@
 // Points where any member, the truth (or the climatology, for ACC) is NaN are NaN in the reference's maps: channel
 // `nan_channel` (SST: NaN over land) averages with nanmean, every other channel with mean (one NaN -> NaN), ACC
 // always with nanmean -- reproduced through the valid-point counts.
+// Two entry points share the per-point body (score_point) and the per-(channel, lead time) finish (finish_point), so they give the
+// same bits: ldc_ensemble_scores (one lead time, optional point maps) and ldc_rollout_scores (every lead time of a decode batch in one
+// launch, grid z = lead time: forecast addressed by member / lead / channel strides, optional fused inverse normalisation, truth and
+// climatology as tables with a slot per lead time, output columns at an offset; the driver of evaluate_ens_gpu.py:268-425).
 #include <math.h>
 
 #include "common.h"
@@ -66,22 +70,38 @@ __device__ __forceinline__ float wave_total(float v) {  // fixed butterfly order
   return v;
 }
 
-template <int NP, int NUSE>  // NUSE = members rounded up to a multiple of 8 (<= NP = next power of two)
-__global__ __launch_bounds__(TPB) void ensemble_scores_kernel(ScoreArgs a) {
+// The inverse normalisation of decode_latent_ens fused into the load (rollout entry point): (v / target_std) * sd + mn, every
+// operation rounded on its own as chan_affine_kernel (layout.hip) and track_gather_kernel (track.hip) round theirs - those files are
+// built with -ffp-contract=off, this one is not, so the contraction is switched off here.  x / 1 == x: the division is skipped
+// for the default target_std.
+struct InvNorm {
+  float target_std, sd, mn;
+  bool unit;  // target_std == 1
+};
+
+__device__ __forceinline__ float inv_norm(float v, const InvNorm& n) {
+#pragma clang fp contract(off)
+  const float q = n.unit ? v : v / n.target_std;
+  const float m = q * n.sd;
+  return m + n.mn;
+}
+
+// One grid point of one (channel, lead time): the M member loads, sort, skill / spread / crps / se, the ACC terms, the validity flags
+// and the fixed-order workgroup reduction of the 15 partial sums into part_dst[NQ + 7].  f / tp / clp point at this thread's point
+// (member 0; clp nullptr = no ACC); skill_dst / spread_dst: this point's map entries or nullptr.  Shared by both entry points, so
+// that they give the same bits.
+template <int NP, int NUSE, bool INV>  // NUSE = members rounded up to a multiple of 8 (<= NP = next power of two)
+__device__ __forceinline__ void score_point(const float* f, long long ms, int M, const float* tp, const float* clp, const float* wp,
+                                            bool in, float* skill_dst, float* spread_dst, float* part_dst, const InvNorm& nrm) {
   __shared__ float red[4][NQ + 7];
-  const int c = blockIdx.y;
-  const int HW = a.H * a.W;
-  const int p = blockIdx.x * TPB + threadIdx.x;
-  const bool in = p < HW;
-  const int pp = in ? p : 0;
-  const float* f = a.fc + static_cast<long long>(c) * a.fc_cs + pp;
   float x[NP];
   bool nan_m = false;
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    if (i < NUSE && i < a.M) {
-      const float v = f[static_cast<long long>(i) * a.fc_ms];
+    if (i < NUSE && i < M) {
+      float v = f[static_cast<long long>(i) * ms];
+      if constexpr (INV) v = inv_norm(v, nrm);
       x[i] = v;
       sum += v;  // same left-to-right order as torch's mean over dim 0 for small M is not guaranteed; tolerance in tests
       nan_m = nan_m || (v != v);
@@ -89,28 +109,28 @@ __global__ __launch_bounds__(TPB) void ensemble_scores_kernel(ScoreArgs a) {
       x[i] = INFINITY;  // sorts behind every member
     }
   }
-  const float t = a.truth[static_cast<long long>(c) * a.tr_cs + pp];
-  const float w = a.lat_w[pp / a.W];
-  const float Mf = static_cast<float>(a.M);
+  const float t = *tp;
+  const float w = *wp;
+  const float Mf = static_cast<float>(M);
   float skill = 0.f;
 #pragma unroll
   for (int i = 0; i < NUSE; ++i)
-    if (i < a.M) skill += fabsf(t - x[i]);
+    if (i < M) skill += fabsf(t - x[i]);
   skill /= Mf;
   float spread = 0.f;
-  if (a.M >= 2) {
+  if (M >= 2) {
     sort_network<NP, NUSE>(x);
     float ws = 0.f;
 #pragma unroll
     for (int i = 0; i < NUSE; ++i)
-      if (i < a.M) ws += x[i] * (2.0f * static_cast<float>(i + 1) - Mf - 1.0f);
+      if (i < M) ws += x[i] * (2.0f * static_cast<float>(i + 1) - Mf - 1.0f);
     spread = 2.0f * ws / (Mf * (Mf - 1.0f));
   }
   const float nanv = __builtin_nanf("");
   if (nan_m) spread = nanv;  // the sort would have dropped the NaNs
   if (in) {
-    if (a.skill_map) a.skill_map[static_cast<long long>(c) * HW + p] = skill;
-    if (a.spread_map) a.spread_map[static_cast<long long>(c) * HW + p] = spread;
+    if (skill_dst) *skill_dst = skill;
+    if (spread_dst) *spread_dst = spread;
   }
   const float mean = sum / Mf;
   const float se = (mean - t) * (mean - t);
@@ -119,8 +139,8 @@ __global__ __launch_bounds__(TPB) void ensemble_scores_kernel(ScoreArgs a) {
   const bool v_skill = in && skill == skill, v_spread = in && spread == spread, v_crps = in && crps == crps, v_se = in && se == se;
   float fa = 0.f, ta = 0.f;
   bool v_acc = false;
-  if (a.clim) {
-    const float cl = a.clim[static_cast<long long>(c) * a.cl_cs + pp];
+  if (clp) {
+    const float cl = *clp;
     fa = mean - cl;
     ta = t - cl;
     // the reference takes three independent nanmeans; a point is dropped from each where that product is NaN
@@ -145,21 +165,69 @@ __global__ __launch_bounds__(TPB) void ensemble_scores_kernel(ScoreArgs a) {
   __syncthreads();
   if (threadIdx.x < NQ + 7) {
     const int i = threadIdx.x;
-    float* dst = a.part + (static_cast<long long>(c) * a.nblk + blockIdx.x) * (NQ + 7);
-    dst[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+    part_dst[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
   }
 }
 
-// out: [5][C] = acc, mse, crps_spread, crps_skill, crps.  One wave per channel: lane j adds the partial records
-// j, j + 64, ... in order, then a fixed butterfly (deterministic).
-__global__ __launch_bounds__(64) void ensemble_scores_finish_kernel(const float* __restrict__ part, int nblk, int C, int nan_channel,
-                                                                    int has_clim, float* __restrict__ out) {
-  const int c = blockIdx.x;
+template <int NP, int NUSE>
+__global__ __launch_bounds__(TPB) void ensemble_scores_kernel(ScoreArgs a) {
+  const int c = blockIdx.y;
+  const int HW = a.H * a.W;
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  const bool in = p < HW;
+  const int pp = in ? p : 0;
+  score_point<NP, NUSE, false>(a.fc + static_cast<long long>(c) * a.fc_cs + pp, a.fc_ms, a.M, a.truth + static_cast<long long>(c) * a.tr_cs + pp,
+                               a.clim ? a.clim + static_cast<long long>(c) * a.cl_cs + pp : nullptr, a.lat_w + pp / a.W, in,
+                               a.skill_map ? a.skill_map + static_cast<long long>(c) * HW + p : nullptr,
+                               a.spread_map ? a.spread_map + static_cast<long long>(c) * HW + p : nullptr,
+                               a.part + (static_cast<long long>(c) * a.nblk + blockIdx.x) * (NQ + 7), InvNorm{});
+}
+
+// Every lead time of a decode batch in one launch: grid (nblk, C, L).  The forecast is addressed by member / lead / channel strides
+// (the (ens, C, T, H, W) array or the decoder's frame-major (L * ens, C, H, W) output), truth and climatology are tables of planes
+// with a slot per lead time; the optional inverse normalisation is applied to every forecast value as it is loaded.
+struct RolloutArgs {
+  const float* fc;
+  const float* truth;
+  const float* clim;   // nullptr = no ACC
+  const float* lat_w;  // [H]
+  const int* tr_slot;  // [L]
+  const int* cl_slot;  // [L]
+  const float* mean;   // [C] or nullptr (forecast already in physical units)
+  const float* sd;     // [C]
+  float target_std;
+  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs, cl_ss, cl_cs;
+  int M, C, H, W;
+  float* part;  // [L][C][nblk][NQ + 7]
+  int nblk;
+};
+
+template <int NP, int NUSE, bool INV>
+__global__ __launch_bounds__(TPB) void rollout_scores_kernel(RolloutArgs a) {
+  const int c = blockIdx.y, l = blockIdx.z;
+  const int HW = a.H * a.W;
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  const bool in = p < HW;
+  const int pp = in ? p : 0;
+  const float* f = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs + pp;
+  const float* tp = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs + pp;
+  const float* clp = a.clim ? a.clim + static_cast<long long>(a.cl_slot[l]) * a.cl_ss + static_cast<long long>(c) * a.cl_cs + pp : nullptr;
+  InvNorm nrm{};
+  if constexpr (INV) nrm = InvNorm{a.target_std, a.sd[c], a.mean[c], a.target_std == 1.0f};
+  score_point<NP, NUSE, INV>(f, a.fc_ms, a.M, tp, clp, a.lat_w + pp / a.W, in, nullptr, nullptr,
+                             a.part + ((static_cast<long long>(l) * a.C + c) * a.nblk + blockIdx.x) * (NQ + 7), nrm);
+}
+
+// The five scores of one (channel, lead time) from its nblk partial records.  One wave: lane j adds the partial records
+// j, j + 64, ... in order, then a fixed butterfly (deterministic); lane 0 holds the result.  dst[k * dst_stride], k < 5 =
+// acc, mse, crps_spread, crps_skill, crps.
+__device__ __forceinline__ void finish_point(const float* __restrict__ part, int nblk, bool nanmean, int has_clim, float* __restrict__ dst,
+                                             long long dst_stride) {
   float s[NQ + 7];
 #pragma unroll
   for (int i = 0; i < NQ + 7; ++i) s[i] = 0.f;
   for (int b = threadIdx.x; b < nblk; b += 64) {
-    const float* src = part + (static_cast<long long>(c) * nblk + b) * (NQ + 7);
+    const float* src = part + static_cast<long long>(b) * (NQ + 7);
 #pragma unroll
     for (int i = 0; i < NQ + 7; ++i) s[i] += src[i];
   }
@@ -170,7 +238,7 @@ __global__ __launch_bounds__(64) void ensemble_scores_finish_kernel(const float*
   const float total = s[14];
   // mean: any NaN point -> NaN; nanmean: average over the valid points (all invalid -> NaN, as torch.nanmean)
   auto avg = [&](float sum, float cnt) {
-    if (c == nan_channel) return cnt > 0.f ? sum / cnt : nanv;
+    if (nanmean) return cnt > 0.f ? sum / cnt : nanv;
     return cnt == total ? sum / total : nanv;
   };
   const float skill = avg(s[0], s[7]), spread = avg(s[1], s[8]), crps = avg(s[2], s[9]), mse = avg(s[3], s[10]);
@@ -179,11 +247,26 @@ __global__ __launch_bounds__(64) void ensemble_scores_finish_kernel(const float*
     const float n4 = s[11] > 0.f ? s[4] / s[11] : nanv, n5 = s[12] > 0.f ? s[5] / s[12] : nanv, n6 = s[13] > 0.f ? s[6] / s[13] : nanv;
     acc = n4 / sqrtf(n5 * n6);
   }
-  out[0 * C + c] = acc;
-  out[1 * C + c] = mse;
-  out[2 * C + c] = spread;
-  out[3 * C + c] = skill;
-  out[4 * C + c] = crps;
+  dst[0 * dst_stride] = acc;
+  dst[1 * dst_stride] = mse;
+  dst[2 * dst_stride] = spread;
+  dst[3 * dst_stride] = skill;
+  dst[4 * dst_stride] = crps;
+}
+
+// out: [5][C] = acc, mse, crps_spread, crps_skill, crps.  One wave per channel.
+__global__ __launch_bounds__(64) void ensemble_scores_finish_kernel(const float* __restrict__ part, int nblk, int C, int nan_channel,
+                                                                    int has_clim, float* __restrict__ out) {
+  const int c = blockIdx.x;
+  finish_point(part + static_cast<long long>(c) * nblk * (NQ + 7), nblk, c == nan_channel, has_clim, out + c, C);
+}
+
+// out: [5][C][L_total], columns l_off .. l_off + L - 1.  One wave per (channel, lead time): grid (C, L).
+__global__ __launch_bounds__(64) void rollout_scores_finish_kernel(const float* __restrict__ part, int nblk, int C, int nan_channel,
+                                                                   int has_clim, float* __restrict__ out, int L_total, int l_off) {
+  const int c = blockIdx.x, l = blockIdx.y;
+  finish_point(part + (static_cast<long long>(l) * C + c) * nblk * (NQ + 7), nblk, c == nan_channel, has_clim,
+               out + static_cast<long long>(c) * L_total + l_off + l, static_cast<long long>(C) * L_total);
 }
 
 }  // namespace
@@ -234,5 +317,70 @@ extern "C" int ldc_ensemble_scores(const float* forecast, long long member_strid
   if (st != LDC_OK) return st;
   hipLaunchKernelGGL(ensemble_scores_finish_kernel, dim3(C), dim3(64), 0, s, a.part, a.nblk, C, nan_channel,
                      clim != nullptr ? 1 : 0, out);
+  return ldc_launch_status();
+}
+
+extern "C" long long ldc_rollout_scores_workspace_bytes(int C, int L, int H, int W) {
+  if (C <= 0 || L <= 0 || H <= 0 || W <= 0) return 0;
+  return static_cast<long long>(L) * ldc_ensemble_scores_workspace_bytes(C, H, W);
+}
+
+namespace {
+template <bool INV>
+void launch_rollout(const RolloutArgs& a, dim3 grid, hipStream_t s) {
+  const int M = a.M;
+  if (M <= 8) hipLaunchKernelGGL((rollout_scores_kernel<8, 8, INV>), grid, dim3(TPB), 0, s, a);
+  else if (M <= 16) hipLaunchKernelGGL((rollout_scores_kernel<16, 16, INV>), grid, dim3(TPB), 0, s, a);
+  else if (M <= 24) hipLaunchKernelGGL((rollout_scores_kernel<32, 24, INV>), grid, dim3(TPB), 0, s, a);
+  else if (M <= 32) hipLaunchKernelGGL((rollout_scores_kernel<32, 32, INV>), grid, dim3(TPB), 0, s, a);
+  else if (M <= 40) hipLaunchKernelGGL((rollout_scores_kernel<64, 40, INV>), grid, dim3(TPB), 0, s, a);
+  else if (M <= 48) hipLaunchKernelGGL((rollout_scores_kernel<64, 48, INV>), grid, dim3(TPB), 0, s, a);
+  else if (M <= 56) hipLaunchKernelGGL((rollout_scores_kernel<64, 56, INV>), grid, dim3(TPB), 0, s, a);
+  else hipLaunchKernelGGL((rollout_scores_kernel<64, 64, INV>), grid, dim3(TPB), 0, s, a);
+}
+}  // namespace
+
+extern "C" int ldc_rollout_scores(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride,
+                                  const float* mean, const float* std_, float target_std, const float* truth,
+                                  long long truth_slot_stride, long long truth_channel_stride, const int* truth_slot, const float* clim,
+                                  long long clim_slot_stride, long long clim_channel_stride, const int* clim_slot,
+                                  const float* lat_weight, int M, int C, int L, int H, int W, int nan_channel, float* out, int L_total,
+                                  int l_off, void* workspace, long long workspace_bytes, void* stream) {
+  LDC_CHECK_PTR(forecast);
+  LDC_CHECK_PTR(truth);
+  LDC_CHECK_PTR(truth_slot);
+  LDC_CHECK_PTR(lat_weight);
+  LDC_CHECK_PTR(out);
+  LDC_CHECK_PTR(workspace);
+  if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
+  if (mean != nullptr) LDC_CHECK_PTR(std_);
+  if (M <= 0 || C <= 0 || L <= 0 || H <= 0 || W <= 0 || L_total <= 0 || l_off < 0) return LDC_ERR_ARG;
+  if (static_cast<long long>(l_off) + L > L_total) return LDC_ERR_ARG;
+  if (M > 64 || C > 65535 || L > 65535) return LDC_ERR_UNSUPPORTED;
+  if (workspace_bytes < ldc_rollout_scores_workspace_bytes(C, L, H, W)) return LDC_ERR_ARG;
+  RolloutArgs a{};
+  a.fc = forecast;
+  a.truth = truth;
+  a.clim = clim;
+  a.lat_w = lat_weight;
+  a.tr_slot = truth_slot;
+  a.cl_slot = clim_slot;
+  a.mean = mean;
+  a.sd = std_;
+  a.target_std = target_std;
+  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
+  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
+  a.cl_ss = clim_slot_stride; a.cl_cs = clim_channel_stride;
+  a.M = M; a.C = C; a.H = H; a.W = W;
+  a.part = static_cast<float*>(workspace);
+  a.nblk = static_cast<int>(ldc_cdiv(static_cast<long long>(H) * W, TPB));
+  dim3 grid(a.nblk, C, L);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mean != nullptr) launch_rollout<true>(a, grid, s);
+  else launch_rollout<false>(a, grid, s);
+  int st = ldc_launch_status();
+  if (st != LDC_OK) return st;
+  hipLaunchKernelGGL(rollout_scores_finish_kernel, dim3(C, L), dim3(64), 0, s, a.part, a.nblk, C, nan_channel, clim != nullptr ? 1 : 0,
+                     out, L_total, l_off);
   return ldc_launch_status();
 }

@@ -103,3 +103,89 @@ def ensemble_scores(dec_t: torch.Tensor, ref_t: torch.Tensor, clim_t: torch.Tens
     ens_acc, ens_mse, crps_spread, crps_skill, crps; channel `sst_channel` is averaged with nanmean, the others with mean."""
     out, _, _ = _scores(dec_t, ref_t, clim_t, lat_weight, sst_channel, False)
     return dict(ens_acc=out[0], ens_mse=out[1], crps_spread=out[2], crps_skill=out[3], crps=out[4])
+
+
+SCORE_NAMES = ("ens_acc", "ens_mse", "crps_spread", "crps_skill", "crps")  # the planes of the kernels' `out`, in order
+
+
+def _plane_table(t: torch.Tensor, slots, C: int, L: int, H: int, W: int, what: str):
+    """truth / climatology for ldc_rollout_scores: -> (tensor, slot_stride, channel_stride, host slot list).  Without slots a
+    (C, L, H, W) tensor, lead l in slot l; with slots an (N, C, H, W) table.  Slots are checked here, on the host: the kernel trusts them."""
+    if t.dtype != torch.float32:
+        raise NotImplementedError("fp32 only")
+    if slots is None:
+        if tuple(t.shape) != (C, L, H, W):
+            raise ValueError(f"{what} must be (C, L, H, W) = {(C, L, H, W)} without slots, got {tuple(t.shape)}")
+        if t.stride(-1) != 1 or t.stride(-2) != W:
+            t = t.contiguous()
+        return t, t.stride(1), t.stride(0), list(range(L))
+    if t.dim() != 4 or tuple(t.shape[1:]) != (C, H, W):
+        raise ValueError(f"{what} must be an (N, C, H, W) = (N, {C}, {H}, {W}) table with slots, got {tuple(t.shape)}")
+    slots = [int(s) for s in (slots.tolist() if isinstance(slots, torch.Tensor) else slots)]
+    if len(slots) != L:
+        raise ValueError(f"{what}: {len(slots)} slots for {L} lead times")
+    if any(not 0 <= s < t.shape[0] for s in slots):
+        raise ValueError(f"{what}: slots {slots} reach outside the table's {t.shape[0]} entries")
+    if t.stride(-1) != 1 or t.stride(-2) != W:
+        t = t.contiguous()
+    return t, t.stride(0), t.stride(1), slots
+
+
+@torch.no_grad()
+def rollout_scores(forecast: torch.Tensor, truth: torch.Tensor, clim: Optional[torch.Tensor], lat_weight: torch.Tensor, sst_channel: int, *,
+                   lead_dim: int = 2, mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, target_std: float = 1.0,
+                   truth_slots=None, clim_slots=None, out: Optional[Dict[str, torch.Tensor]] = None,
+                   lead_offset: int = 0) -> Dict[str, torch.Tensor]:
+    """Every lead time of evaluate/evaluate_ens_gpu.py:339-425 in one launch (`ldc_rollout_scores`): column l of each result holds the
+    bits `ensemble_scores` gives for lead time l.
+
+    forecast: (ens, C, L, H, W), or with `lead_dim=0` the (L, ens, C, H, W) view of the decoder's frame-major output; any member / lead /
+    channel strides, the (H, W) plane contiguous.  `mean` / `std` (C,) device vectors and `target_std`: the forecast is still normalised
+    and every value is de-normalised as it is loaded, (x / target_std) * std[c] + mean[c] - bit-equal to scoring
+    `inverse_normalize_transform_3D(forecast, mean, std, target_std)`.  truth / clim: (C, L, H, W), or with `truth_slots` / `clim_slots`
+    (one host int per lead time) an (N, C, H, W) table of which lead l reads entry slots[l] (a year of frames, the (366 x 4)
+    climatology); clim None = no ACC; they are never transformed.  Returns the dict of five (C, L_total) device tensors under
+    `ensemble_scores`' names: a fresh one (L_total = lead_offset + L, unwritten columns NaN), or `out` - the dict an earlier call
+    returned - of which columns lead_offset .. lead_offset + L - 1 are written."""
+    hip._dev(forecast, truth, clim, lat_weight, mean, std)
+    if forecast.dim() != 5 or lead_dim not in (0, 2):
+        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
+    if forecast.dtype != torch.float32:
+        raise NotImplementedError("fp32 only")
+    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
+    M, C, L, H, W = f.shape
+    if f.stride(-1) != 1 or f.stride(-2) != W:
+        f = f.contiguous()
+    dev = f.device
+    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slots, C, L, H, W, "truth")
+    c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
+    w = lat_weight.to(dev, torch.float32).reshape(-1).contiguous()
+    if w.numel() != H:
+        raise ValueError("lat_weight must have one value per latitude row")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
+        if mean.numel() != C or std.numel() != C:
+            raise ValueError(f"mean / std must hold one value per channel ({C})")
+    if out is None:
+        buf = torch.full((5, C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
+    else:
+        buf = getattr(out, "_buffer", None) if not isinstance(out, torch.Tensor) else out
+        if buf is None or buf.dim() != 3 or buf.shape[:2] != (5, C) or not buf.is_contiguous() or buf.dtype != torch.float32 or buf.device != dev:
+            raise ValueError("out must be the dict an earlier rollout_scores call returned (or its contiguous (5, C, L_total) fp32 buffer)")
+    slots = torch.tensor([t_slots, c_slots if c_slots is not None else t_slots], dtype=torch.int32)
+    slots = hip.upload_nonblocking(slots, dev)
+    hip.rollout_scores(f, t, slots[0], c, None if c is None else slots[1], w, buf, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0),
+                       lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs,
+                       clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mean, std=std, target_std=target_std, nan_channel=sst_channel,
+                       L_total=buf.shape[2], l_off=lead_offset)
+    return ScoreDict(buf)
+
+
+class ScoreDict(dict):
+    """{name: (C, L_total) view} over one contiguous (5, C, L_total) device buffer: the five arrays travel to the host in one copy"""
+
+    def __init__(self, buf: torch.Tensor):
+        super().__init__({k: buf[i] for i, k in enumerate(SCORE_NAMES)})
+        self._buffer = buf

@@ -104,6 +104,8 @@ def _load():
         "ldc_relu_linear_attn_nhwc_fmt": (I, [P, P, I, I, I, I, I, F, I, P, L, P]),
         "ldc_ensemble_scores_workspace_bytes": (L, [I, I, I]),
         "ldc_ensemble_scores": (I, [P, L, L, P, L, P, L, P, I, I, I, I, I, P, P, P, P, L, P]),
+        "ldc_rollout_scores_workspace_bytes": (L, [I, I, I, I]),
+        "ldc_rollout_scores": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, I, P, I, I, P, L, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
         "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
         "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
@@ -364,6 +366,19 @@ def ensemble_scores(forecast, truth, clim, lat_weight, out, *, M, C, H, W, membe
     _check(lib.ldc_ensemble_scores(_p(forecast), member_stride, channel_stride, _p(truth), truth_channel_stride, _p(clim),
                                    clim_channel_stride, _p(lat_weight), M, C, H, W, nan_channel, _p(out), _p(skill_map), _p(spread_map),
                                    _p(ws), ws.numel() * 4, _stream()), "ldc_ensemble_scores")
+
+
+def rollout_scores(forecast, truth, truth_slot, clim, clim_slot, lat_weight, out, *, M, C, L, H, W, member_stride, lead_stride, channel_stride,
+                   truth_slot_stride, truth_channel_stride, clim_slot_stride=0, clim_channel_stride=0, mean=None, std=None, target_std=1.0,
+                   nan_channel=-1, L_total, l_off=0):
+    """out [5][C][L_total], columns l_off .. l_off + L - 1 = acc, mse, crps_spread, crps_skill, crps of L lead times in one launch
+    (ladcast_hip.h: ldc_rollout_scores); truth_slot / clim_slot: device int32 [L]"""
+    _dev(forecast, truth, truth_slot, clim, clim_slot, lat_weight, out, mean, std)
+    ws = _workspace("rollout_scores", forecast.device, int(lib.ldc_rollout_scores_workspace_bytes(C, L, H, W)), grow=True)
+    _check(lib.ldc_rollout_scores(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
+                                  truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(clim), clim_slot_stride, clim_channel_stride,
+                                  _p(clim_slot), _p(lat_weight), M, C, L, H, W, nan_channel, _p(out), L_total, l_off, _p(ws), ws.numel() * 4,
+                                  _stream()), "ldc_rollout_scores")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):

@@ -34,3 +34,39 @@ t_torch = timed(torch_ops, 5)
 nbytes = dec.numel() * 4 + 2 * ref.numel() * 4
 print(f"ens={M}: ldc_ensemble_scores {t_hip * 1e6:.1f} us = {nbytes / t_hip / 1e12:.2f} TB/s of algorithmic bytes ({nbytes / 1e6:.0f} MB read once); "
       f"torch op sequence on the same GPU {t_torch * 1e6:.1f} us ({t_torch / t_hip:.1f}x)")
+
+# rollout leg: L lead times of a decoder's frame-major, still normalised output in ONE ldc_rollout_scores launch (inverse normalisation
+# fused) against what it replaces - a chan_affine pass over the batch, then one ldc_ensemble_scores launch per lead time.  HIP events.
+from ladcast_amd.pipelines.utils import inverse_normalize_transform_3D
+
+L = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+frames = (torch.randn(L * M, C, H, W, generator=g) * 0.5).cuda()  # (L * ens, C, H, W), lead-major then member
+truth_t, clim_t = torch.randn(L, C, H, W, generator=g).cuda(), torch.randn(L, C, H, W, generator=g).cuda()
+mean, std = torch.randn(C, generator=g).cuda(), (torch.rand(C, generator=g) + 0.5).cuda()
+slots = list(range(L))
+out = torch.empty(5, C, L, device="cuda")
+
+
+def timed_events(fn, n=10):
+    for _ in range(3): fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n): fn()
+    b.record(); torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e-3 / n
+
+
+def fused():
+    E.rollout_scores(frames.view(L, M, C, H, W), truth_t, clim_t, w, sst, lead_dim=0, mean=mean, std=std, truth_slots=slots, clim_slots=slots, out=out)
+
+
+def separate():
+    phys = inverse_normalize_transform_3D(frames.view(L * M, C, 1, H, W), mean, std).view(L, M, C, H, W)
+    for l in range(L):
+        E.ensemble_scores(phys[l], truth_t[l], clim_t[l], w, sst)
+
+
+t_fused, t_sep = timed_events(fused), timed_events(separate)
+nbytes = frames.numel() * 4 + 2 * truth_t.numel() * 4
+print(f"ens={M}, {L} lead times: ldc_rollout_scores (fused inverse normalisation) {t_fused * 1e3:.2f} ms = {nbytes / t_fused / 1e12:.2f} TB/s of algorithmic bytes "
+      f"({nbytes / 1e6:.0f} MB read once); chan_affine pass + {L} ldc_ensemble_scores launches {t_sep * 1e3:.2f} ms ({t_sep / t_fused:.2f}x)")
