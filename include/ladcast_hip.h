@@ -539,6 +539,22 @@ int ldc_rollout_scores(const float* forecast, long long member_stride, long long
                        long long clim_channel_stride, const int* clim_slot, const float* lat_weight, int M, int C, int L, int H,
                        int W, int nan_channel, float* out, int L_total, int l_off, void* workspace, long long workspace_bytes,
                        void* stream);
+/* The three scores of the reference's validation hook (ladcast/train_AR.py:281-312) for every lead time of a decode batch in one launch
+ * (additive under ABI 5).  Addressing of forecast, inverse normalisation, truth table, lat_weight, out columns and workspace exactly as
+ * ldc_rollout_scores; there is no climatology and no nanmean channel: every average is a plain mean, so one NaN among a point's members
+ * or in its truth makes all three scores of that (channel, lead time) NaN and leaves every other one alone.
+ *   out [3][C][L_total] = ens_mse, single_mse, crps:
+ *     ens_mse    = mean_hw[(mean_i x_i - t)^2 w(lat)]
+ *     single_mse = mean_{i,hw}[(x_i - t)^2 w(lat)]   (sum over the members in member order, / M, per point)
+ *     crps       = mean_hw[(skill - spread / 2) w(lat)]
+ *   Same point body, arms (M <= 64) and reduction order as ldc_rollout_scores: ens_mse and crps hold the bits its `ens_mse` and `crps`
+ *   give with clim == NULL and nan_channel == -1; at M == 1 single_mse holds the bits of ens_mse.  No float atomics: run-to-run bit-equal.
+ * Errors as ldc_rollout_scores, with ldc_validation_scores_workspace_bytes(C, L, H, W). */
+long long ldc_validation_scores_workspace_bytes(int C, int L, int H, int W);
+int ldc_validation_scores(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride,
+                          const float* mean, const float* std_, float target_std, const float* truth, long long truth_slot_stride,
+                          long long truth_channel_stride, const int* truth_slot, const float* lat_weight, int M, int C, int L, int H,
+                          int W, float* out, int L_total, int l_off, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

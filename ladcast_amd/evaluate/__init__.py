@@ -1,9 +1,11 @@
-from .utils import (ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor, get_normalized_lat_weights_based_on_cos,
-                    pointwise_crps_skill, pointwise_crps_spread, rollout_scores)
+from .utils import (VALIDATION_SCORE_NAMES, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
+                    get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_scores, validation_scores)
 
 _DRIVER_NAMES = ("climatology_slots", "score_latent_rollout", "truth_frame_slots")  # evaluate_ens_gpu's, resolved at first use: the
-__all__ = ["ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor", "get_normalized_lat_weights_based_on_cos",  # module
-           "pointwise_crps_skill", "pointwise_crps_spread", "rollout_scores", *_DRIVER_NAMES]  # also runs as `python -m`
+_VALIDATE_NAMES = ("NpyLatentStore", "log_validation", "validate_initial_time")  # validate_AR's, likewise
+__all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
+           "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_scores",  # also runs
+           "validation_scores", *_DRIVER_NAMES, *_VALIDATE_NAMES]  # as `python -m`
 
 
 def __getattr__(name):
@@ -11,4 +13,8 @@ def __getattr__(name):
         from . import evaluate_ens_gpu
 
         return getattr(evaluate_ens_gpu, name)
+    if name in _VALIDATE_NAMES:
+        from . import validate_AR
+
+        return getattr(validate_AR, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -184,8 +184,57 @@ def rollout_scores(forecast: torch.Tensor, truth: torch.Tensor, clim: Optional[t
 
 
 class ScoreDict(dict):
-    """{name: (C, L_total) view} over one contiguous (5, C, L_total) device buffer: the five arrays travel to the host in one copy"""
+    """{name: (C, L_total) view} over one contiguous (len(names), C, L_total) device buffer: the arrays travel to the host in one copy"""
 
-    def __init__(self, buf: torch.Tensor):
-        super().__init__({k: buf[i] for i, k in enumerate(SCORE_NAMES)})
+    def __init__(self, buf: torch.Tensor, names=SCORE_NAMES):
+        super().__init__({k: buf[i] for i, k in enumerate(names)})
         self._buffer = buf
+
+
+VALIDATION_SCORE_NAMES = ("ens_mse", "single_mse", "crps")  # the planes of ldc_validation_scores' `out`, in order
+
+
+@torch.no_grad()
+def validation_scores(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torch.Tensor, *, lead_dim: int = 2,
+                      mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, target_std: float = 1.0, truth_slots=None,
+                      out: Optional[Dict[str, torch.Tensor]] = None, lead_offset: int = 0) -> Dict[str, torch.Tensor]:
+    """The three scores of the validation hook (train_AR.py:281-312) for every lead time in one launch (`ldc_validation_scores`):
+        ens_mse = mean_hw[(mean_i x_i - t)^2 w],  single_mse = mean_{i,hw}[(x_i - t)^2 w],  crps = mean_hw[(skill - spread / 2) w]
+    with the plain mean everywhere: one NaN among a point's members or in its truth makes the three scores of that (channel, lead time)
+    NaN.  `ens_mse` and `crps` hold the bits `rollout_scores(forecast, truth, None, lat_weight, -1, ...)` gives.
+
+    forecast, `lead_dim`, `mean` / `std` / `target_std`, truth / `truth_slots`, `out` / `lead_offset`: as `rollout_scores`.  Returns the
+    dict of three (C, L_total) device tensors over one contiguous (3, C, L_total) buffer (`VALIDATION_SCORE_NAMES`); unwritten columns of
+    a fresh one are NaN."""
+    hip._dev(forecast, truth, lat_weight, mean, std)
+    if forecast.dim() != 5 or lead_dim not in (0, 2):
+        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
+    if forecast.dtype != torch.float32:
+        raise NotImplementedError("fp32 only")
+    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
+    M, C, L, H, W = f.shape
+    if f.stride(-1) != 1 or f.stride(-2) != W:
+        f = f.contiguous()
+    dev = f.device
+    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slots, C, L, H, W, "truth")
+    w = lat_weight.to(dev, torch.float32).reshape(-1).contiguous()
+    if w.numel() != H:
+        raise ValueError("lat_weight must have one value per latitude row")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
+        if mean.numel() != C or std.numel() != C:
+            raise ValueError(f"mean / std must hold one value per channel ({C})")
+    n = len(VALIDATION_SCORE_NAMES)
+    if out is None:
+        buf = torch.full((n, C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
+    else:
+        buf = getattr(out, "_buffer", None) if not isinstance(out, torch.Tensor) else out
+        if buf is None or buf.dim() != 3 or buf.shape[:2] != (n, C) or not buf.is_contiguous() or buf.dtype != torch.float32 or buf.device != dev:
+            raise ValueError(f"out must be the dict an earlier validation_scores call returned (or its contiguous ({n}, C, L_total) fp32 buffer)")
+    slots = hip.upload_nonblocking(torch.tensor(t_slots, dtype=torch.int32), dev)
+    hip.validation_scores(f, t, slots, w, buf, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
+                          channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
+                          target_std=target_std, L_total=buf.shape[2], l_off=lead_offset)
+    return ScoreDict(buf, VALIDATION_SCORE_NAMES)

@@ -106,6 +106,8 @@ def _load():
         "ldc_ensemble_scores": (I, [P, L, L, P, L, P, L, P, I, I, I, I, I, P, P, P, P, L, P]),
         "ldc_rollout_scores_workspace_bytes": (L, [I, I, I, I]),
         "ldc_rollout_scores": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, I, P, I, I, P, L, P]),
+        "ldc_validation_scores_workspace_bytes": (L, [I, I, I, I]),
+        "ldc_validation_scores": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, P, I, I, P, L, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
         "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
         "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
@@ -379,6 +381,17 @@ def rollout_scores(forecast, truth, truth_slot, clim, clim_slot, lat_weight, out
                                   truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(clim), clim_slot_stride, clim_channel_stride,
                                   _p(clim_slot), _p(lat_weight), M, C, L, H, W, nan_channel, _p(out), L_total, l_off, _p(ws), ws.numel() * 4,
                                   _stream()), "ldc_rollout_scores")
+
+
+def validation_scores(forecast, truth, truth_slot, lat_weight, out, *, M, C, L, H, W, member_stride, lead_stride, channel_stride,
+                      truth_slot_stride, truth_channel_stride, mean=None, std=None, target_std=1.0, L_total, l_off=0):
+    """out [3][C][L_total], columns l_off .. l_off + L - 1 = ens_mse, single_mse, crps of L lead times in one launch
+    (ladcast_hip.h: ldc_validation_scores); truth_slot: device int32 [L]"""
+    _dev(forecast, truth, truth_slot, lat_weight, out, mean, std)
+    ws = _workspace("validation_scores", forecast.device, int(lib.ldc_validation_scores_workspace_bytes(C, L, H, W)), grow=True)
+    _check(lib.ldc_validation_scores(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
+                                     truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(lat_weight), M, C, L, H, W, _p(out), L_total,
+                                     l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_validation_scores")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):
