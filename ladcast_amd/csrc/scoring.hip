@@ -145,7 +145,7 @@ __device__ __forceinline__ void score_point(const float* f, long long ms, int M,
     spread = 2.0f * ws / (Mf * (Mf - 1.0f));
   }
   const float nanv = __builtin_nanf("");
-  if (nan_m) spread = nanv;  // the sort would have dropped the NaNs
+  if (nan_m && M >= 2) spread = nanv;  // the sort would have dropped the NaNs; one member: the reference's spread is zeros, NaN or not
   if (in) {
     if (skill_dst) *skill_dst = skill;
     if (spread_dst) *spread_dst = spread;
