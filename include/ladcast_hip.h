@@ -637,6 +637,33 @@ int ldc_recon_scores(const float* pred, const float* target, const float* static
                      int S, int H, int W, int sst_channel, float* rel, float* abs_norm, float* lw_mse, void* workspace,
                      long long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Dataset statistics (moments.hip; reference ladcast/preprocecss/compute_mean_std_era5.py, and the latent statistics JSON the
+ * reference ships without code).  Additive: ABI 5.
+ * Per channel c < C, over all non-NaN values of x[b*batch_stride + c*channel_stride + h*row_stride + w], b < B, h < H, w < W (fp32;
+ * strided as in ldc_recon_preprocess: the south-pole crop is the caller's row offset, a dropped channel a smaller C, no copy):
+ *   state[c] = { n, mean, M2 } (fp64): the count, the mean and the sum of squared deviations from the mean; the population
+ *   variance is M2 / n.  Only NaN is skipped (+-inf is a value like any other and makes the channel's mean and M2 inf / NaN).
+ *   accumulate == 0: the state is overwritten, whatever it held.  accumulate != 0: the batch's moments are merged into it by Chan's
+ *   pairwise update (a state with n == 0, or n not a positive number, is replaced; a batch without a valid value leaves it alone),
+ *   so a dataset streamed in batches of any size gives the statistics of the whole.  A channel that never saw a valid value has
+ *   n = 0 and mean = M2 = NaN (numpy's nanmean).
+ * All arithmetic is fp64.  A plane is cut into chunks of <= 4096 values, each reduced around its own mean as pivot (corrected two-pass,
+ * the values held in registers: one pass over memory); the chunk records (n, mean, M2) go to the workspace and a second launch merges a
+ * channel's records in index order, again around their mean, and then into the state.  No float atomics: the same call sequence gives
+ * the same bits.  The mean of one call is within about one fp64 ulp of |mean| plus ~2^-48 of the standard deviation, M2 within ~2^-47
+ * relative; each accumulate adds up to half an ulp of |mean|.  A constant channel gives M2 = 0 exactly (while n * |value| is exact in
+ * fp64: fewer than 2^29 values per call).
+ * 16-byte loads when W % 4 == 0 and x and the three strides keep 16-byte alignment; a scalar path otherwise.
+ * LDC_ERR_ARG: a null pointer, a non-positive size, row_stride < W, or a workspace smaller than
+ * ldc_field_moments_workspace_bytes(B, C, H, W); LDC_ERR_ALIGN: workspace not 16-byte, state not 8-byte or x not 4-byte aligned;
+ * LDC_ERR_UNSUPPORTED: more than 2^24 - 1 chunk records, B * C * ceil(H / rows) * ceil(W / 4096) with rows = max(1, 4096 / W) (the
+ * grid of the first launch; ldc_field_moments_workspace_bytes returns 0 then).  Nothing is launched or written on an error.
+ * workspace: 32 bytes per record, no initialisation needed. */
+long long ldc_field_moments_workspace_bytes(int B, int C, int H, int W);
+int ldc_field_moments(const float* x, long long batch_stride, long long channel_stride, long long row_stride, int B, int C, int H,
+                      int W, double* state, int accumulate, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,8 @@ def _load():
         "ldc_recon_preprocess": (I, [P, L, L, L, I, I, I, I, P, P, I, P, P, P]),
         "ldc_recon_scores_workspace_bytes": (L, [I, I, I, I]),
         "ldc_recon_scores": (I, [P, P, P, L, P, P, P, P, I, I, I, I, I, I, P, P, P, P, L, P]),
+        "ldc_field_moments_workspace_bytes": (L, [I, I, I, I]),
+        "ldc_field_moments": (I, [P, L, L, L, I, I, I, I, P, I, P, L, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -409,6 +411,16 @@ def recon_scores(pred, target, static, nan_mask, lat_weight, mean, std, rel, lw_
     ws = _workspace("recon_scores", pred.device, int(lib.ldc_recon_scores_workspace_bytes(B, C + S, H, W)), grow=True)
     _check(lib.ldc_recon_scores(_p(pred), _p(target), _p(static), static_batch_stride, _p(nan_mask), _p(lat_weight), _p(mean), _p(std), B, C, S,
                                 H, W, sst_channel, _p(rel), _p(abs_norm), _p(lw_mse), _p(ws), ws.numel() * 4, _stream()), "ldc_recon_scores")
+
+
+def field_moments(x, state, *, B, C, H, W, batch_stride, channel_stride, row_stride, accumulate):
+    """state [C][3] fp64 = (n, mean, M2) of the non-NaN values of the strided fp32 batch x, overwritten or merged into
+    (ladcast_hip.h: ldc_field_moments)"""
+    _dev(x, state)
+    nbytes = int(lib.ldc_field_moments_workspace_bytes(B, C, H, W))
+    ws = _workspace("field_moments", x.device, max(nbytes, 16), grow=True)
+    _check(lib.ldc_field_moments(_p(x), batch_stride, channel_stride, row_stride, B, C, H, W, _p(state), 1 if accumulate else 0, _p(ws),
+                                 ws.numel() * 4, _stream()), "ldc_field_moments")
 
 
 def compact_rope_table(cos, sin):
