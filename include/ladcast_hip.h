@@ -397,6 +397,31 @@ int ldc_scale_f32(const float* x, float s, float* y, long long n, void* stream);
 int ldc_axpby_f32(const float* x, float a, const float* y, float b, float* out, long long n, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * The EDM denoising objective around the forward, one noise level PER SAMPLE (train_AR.py:873-1032 without the backward
+ * pass).  Tensors: contiguous fp32 (B, C, T, H, W); sample of element i: i / n_per_sample; latitude row: (i / W) % H.
+ * sigma / c_in / c_skip / c_out / weight: fp32 device vectors [B] the host computed with the reference's fp32 tensor
+ * expressions.  No product-sum is contracted: noisy, x_in and denoised are bit-identical to torch's elementwise results.
+ * LDC_ERR_ARG: a null pointer or a non-positive size; LDC_ERR_UNSUPPORTED: more blocks than a grid holds.
+ * ------------------------------------------------------------------------- */
+/* noisy = clean + noise * sigma_b (a product, then a sum); x_in = noisy * c_in_b.  One launch for the batch.
+ * noise == NULL: noisy = clean (precondition_inputs of an already noised tensor; sigma unused).  noisy or x_in may be NULL
+ * (not both): that output is not written (c_in unused without x_in). */
+int ldc_edm_noise_inputs(const float* clean, const float* noise, const float* sigma, const float* c_in, float* noisy,
+                         float* x_in, int B, long long n_per_sample, void* stream);
+/* denoised = c_skip_b * noisy + c_out_b * F (three roundings: scheduler.precondition_outputs) on (B, C, T, plane) views that
+ * may be T-slices of larger tensors: `*_frames` = frames of the tensor the view was sliced from (>= T), i.e. its channel
+ * stride is frames * plane and its batch stride C * frames * plane; the pointer is the view's first element. */
+int ldc_edm_denoise(const float* noisy, const float* F, const float* c_skip, const float* c_out, float* denoised, int B,
+                    int C, int T, int plane, int noisy_frames, int f_frames, int denoised_frames, void* stream);
+/* table[b][c][t] = mean over the (H, W) plane of  w * ((c_skip_b * noisy + c_out_b * F) - target)^2,  w = weight_b, or
+ * (lat_weight[h] * weight_b) with lat_weight [H] (NULL: none): every term in fp32 in that order, summed in fp64 in a fixed
+ * order (one wave per plane, fixed lane assignment, butterfly; no atomics - two launches give the same bits), divided and
+ * rounded once to fp32.  denoised (NULL: not written): the preconditioned output, as ldc_edm_denoise. */
+int ldc_edm_denoise_loss(const float* noisy, const float* F, const float* target, const float* c_skip, const float* c_out,
+                         const float* weight, const float* lat_weight, float* table, float* denoised, int B, int C, int T,
+                         int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------
  * DCAE encoder / decoder (models/DCAE.py, models/sphere_conv.py) in NHWC layout
  * ([B][H][W][C], channel stride 1, pixel stride ld*).
  * ------------------------------------------------------------------------- */

@@ -130,6 +130,9 @@ def _load():
         "ldc_ddpm_step": (I, [P, P, P, P, P, F, F, F, F, F, F, I, L, P]),
         "ldc_scale_f32": (I, [P, F, P, L, P]),
         "ldc_axpby_f32": (I, [P, F, P, F, P, L, P]),
+        "ldc_edm_noise_inputs": (I, [P, P, P, P, P, P, I, L, P]),
+        "ldc_edm_denoise": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+        "ldc_edm_denoise_loss": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
         "ldc_sphere_conv_nhwc": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
         "ldc_sphere_dwconv_nhwc": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
         "ldc_grouped_conv1x1_nhwc": (I, [P, P, P, L, I, I, I, P]),
@@ -701,6 +704,73 @@ def scale_f32(x, s, y):
 def axpby_f32(x, a, y, b, out):
     _dev(x, y, out)
     _check(lib.ldc_axpby_f32(_p(x), a, _p(y), b, _p(out), x.numel(), _stream()), "ldc_axpby_f32")
+
+
+# -- EDM denoising objective, one noise level per sample (ladcast_hip.h: ldc_edm_noise_inputs / _denoise / _denoise_loss) -------------
+def _f32c(what, *ts):
+    for t in ts:
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous()):
+            raise TypeError(f"{what}: contiguous fp32 tensors only")
+
+
+def _per_sample(what, B, *vs):
+    for v in vs:
+        if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == B):
+            raise ValueError(f"{what}: per-sample coefficients are contiguous fp32 device vectors with one entry per sample ({B})")
+
+
+def edm_noise_inputs(clean, noise, sigma, c_in, noisy, x_in):
+    """noisy = clean + noise * sigma_b, x_in = noisy * c_in_b in one launch; noise None: noisy = clean; noisy or x_in None: not written"""
+    _dev(clean, noise, sigma, c_in, noisy, x_in)
+    _f32c("edm_noise_inputs", clean, noise, noisy, x_in)
+    B = clean.shape[0]
+    _per_sample("edm_noise_inputs", B, sigma, c_in)
+    for t in (noise, noisy, x_in):
+        if t is not None and t.shape != clean.shape:
+            raise ValueError("edm_noise_inputs: all tensors have the shape of `clean`")
+    _check(lib.ldc_edm_noise_inputs(_p(clean), _p(noise), _p(sigma), _p(c_in), _p(noisy), _p(x_in), B, clean.numel() // max(B, 1), _stream()),
+           "ldc_edm_noise_inputs")
+
+
+def _t_slice_frames(what, t, shape):
+    """frames of the contiguous (B, C, frames, H, W) tensor that `t` (shape (B, C, T, H, W)) is a T-slice of"""
+    B, C, T, H, W = shape
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32:
+        raise ValueError(f"{what}: fp32 tensors of one shape (B, C, T, H, W)")
+    plane = H * W
+    sb, sc, st, sh, sw = t.stride()
+    ok = (sw == 1 or W == 1) and (sh == W or H == 1) and (st == plane or T == 1)
+    frames = sc // plane if C > 1 else (sb // (C * plane) if B > 1 else T)
+    ok = ok and frames >= T and (C == 1 or sc == frames * plane) and (B == 1 or sb == C * frames * plane)
+    if not ok:
+        raise ValueError(f"{what}: tensors must be contiguous or slices along T of contiguous tensors (strides {t.stride()})")
+    return frames
+
+
+def edm_denoise(noisy, F, c_skip, c_out, denoised):
+    """denoised = c_skip_b * noisy + c_out_b * F; the three (B, C, T, H, W) tensors may be slices along T of contiguous tensors"""
+    _dev(noisy, F, c_skip, c_out, denoised)
+    B, C, T, H, W = noisy.shape
+    _per_sample("edm_denoise", B, c_skip, c_out)
+    fr = [_t_slice_frames("edm_denoise", t, noisy.shape) for t in (noisy, F, denoised)]
+    _check(lib.ldc_edm_denoise(_p(noisy), _p(F), _p(c_skip), _p(c_out), _p(denoised), B, C, T, H * W, fr[0], fr[1], fr[2], _stream()),
+           "ldc_edm_denoise")
+
+
+def edm_denoise_loss(noisy, F, target, c_skip, c_out, weight, table, lat_weight=None, denoised=None):
+    """table (B, C, T) = plane means of w * ((c_skip_b * noisy + c_out_b * F) - target)^2, w = weight_b or lat_weight[h] * weight_b
+    (ladcast_hip.h: ldc_edm_denoise_loss); denoised: also write the preconditioned output"""
+    _dev(noisy, F, target, c_skip, c_out, weight, table, lat_weight, denoised)
+    _f32c("edm_denoise_loss", noisy, F, target, table, lat_weight, denoised)
+    B, C, T, H, W = noisy.shape
+    _per_sample("edm_denoise_loss", B, c_skip, c_out, weight)
+    for t in (F, target, denoised):
+        if t is not None and t.shape != noisy.shape:
+            raise ValueError("edm_denoise_loss: noisy, F, target and denoised have one shape (B, C, T, H, W)")
+    if table.numel() != B * C * T or (lat_weight is not None and lat_weight.numel() != H):
+        raise ValueError("edm_denoise_loss: table holds B * C * T values, lat_weight H")
+    _check(lib.ldc_edm_denoise_loss(_p(noisy), _p(F), _p(target), _p(c_skip), _p(c_out), _p(weight), _p(lat_weight), _p(table), _p(denoised),
+                                    B, C, T, H, W, _stream()), "ldc_edm_denoise_loss")
 
 
 # -- DCAE (NHWC) -------------------------------------------------------------------------------

@@ -43,6 +43,22 @@ def convert_datetime_to_int(dt) -> int:
     return int(dt.strftime("%Y%m%d%H"))
 
 
+def get_sigmas(noise_scheduler, timesteps, n_dim=4, dtype=torch.float32, device="cpu"):
+    """The scheduler's sigma of every entry of `timesteps` (values of `noise_scheduler.timesteps`), shaped (B, 1, ...) with `n_dim`
+    dims for broadcasting against the noised tensor (the contract of the reference's pipelines/utils.py `get_sigmas`).  A timestep
+    must match exactly one schedule entry; anything else is an error, as there.  Host-sized arithmetic: B values."""
+    table = noise_scheduler.sigmas.to(device=device, dtype=dtype)
+    schedule = noise_scheduler.timesteps.to(device)
+    rows = []
+    for t in timesteps.to(device):
+        hit = torch.nonzero(schedule == t)
+        if hit.numel() != 1:
+            raise RuntimeError(f"get_sigmas: timestep {float(t)} matches {hit.numel()} entries of the scheduler's timesteps")
+        rows.append(int(hit))
+    sigma = table[rows].reshape(-1)
+    return sigma.reshape(sigma.shape + (1,) * max(0, n_dim - 1))
+
+
 # -- per-channel latent / field transforms (dataloader/utils.py:223-269) on the device ----------
 _host_to_device = hip.upload_nonblocking
 

@@ -17,8 +17,9 @@ this table; the numbers are rel-L2 against the fp32 CPU oracle on identical weig
 MODES = ("fp32", "bf16x3", "bf16")
 
 STATED_TOLERANCE = {
-    "fp32": {"forward": 2e-5, "chunk": 1e-4, "rollout": 1e-4, "dcae": 1e-4},
-    "bf16x3": {"forward": 3e-5, "chunk": 1e-4, "rollout": 1e-4, "dcae": 1e-4},
+    # "denoise_loss": relative difference of the denoising loss (evaluate/denoise_loss.py) to the reference's fp32 loss - see DENOISE_LOSS_FACTOR
+    "fp32": {"forward": 2e-5, "chunk": 1e-4, "rollout": 1e-4, "dcae": 1e-4, "denoise_loss": 2.5e-5},
+    "bf16x3": {"forward": 3e-5, "chunk": 1e-4, "rollout": 1e-4, "dcae": 1e-4, "denoise_loss": 3.75e-5},
     "bf16": {
         # AR transformer (375M and tiny widths): one forward; network output inside a sampler chunk (its input has drifted); the
         # sample of a 20-step chunk with the 39-forward Heun sampler / the 20-forward DPM-Solver++(2M) loop
@@ -35,8 +36,17 @@ STATED_TOLERANCE = {
         "dcae_decode": 1.2e-2,
         # end to end: encode -> chained chunks -> decode, decoded fields of chunk c (every chunk, no growth allowed beyond it)
         "rollout_decoded": 2.5e-2,
+        "denoise_loss": 8.75e-3,
     },
 }
+
+# "denoise_loss" = DENOISE_LOSS_FACTOR x "forward", DERIVED, not fitted: the loss is L = mean(w (c_skip x + c_out F - y)^2) and the EDM
+# weight satisfies w c_out^2 = 1 for every sigma, so an error dF of the network output with rel-L2 eps moves it by
+# |dL| <= 2 sqrt(L) sqrt(mean(m dF^2)) <= 2 sqrt(m_max) eps rms(F) sqrt(L)  (Cauchy-Schwarz; m = latitude weight, m_max = 1.44 for the 15
+# rows at -83.25 .. 84.75, 1 without), i.e. |dL| / L <= 2 * 1.2 * eps * rms(F) / sqrt(L).  On the fixture of
+# tests/golden/denoise_loss_ref.npz the REFERENCE's own numbers are rms(F) = 0.605 and L >= 1.357: a factor 1.25.  The loss arithmetic
+# itself (fp32 terms, fp64 sums) adds about one fp32 ulp, 1e-7.
+DENOISE_LOSS_FACTOR = 1.25
 
 
 def tolerance(mode: str, stage: str) -> float:

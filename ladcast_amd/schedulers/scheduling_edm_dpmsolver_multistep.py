@@ -8,7 +8,8 @@ The reference builds ``diffusers.EDMDPMSolverMultistepScheduler`` with default k
 Split of work: the schedule (Karras sigmas, step indices, the per-step scalar coefficients)
 is host arithmetic on fp32 torch CPU scalars, exactly where diffusers computes it, so the
 indexing is bit-exact; every whole-tensor update runs in a HIP kernel
-(``ldc_scale_f32`` / ``ldc_axpby_f32`` / ``ldc_dpm_step``).
+(``ldc_scale_f32`` / ``ldc_axpby_f32`` / ``ldc_dpm_step``; with one sigma per sample, as the training objective draws them,
+``ldc_edm_noise_inputs`` / ``ldc_edm_denoise``).
 """
 from __future__ import annotations
 
@@ -115,12 +116,31 @@ class EDMDPMSolverMultistepScheduler:
             sigma = torch.tensor([sigma])
         return 0.25 * torch.log(sigma)
 
+    def edm_coefficients(self, sigmas):
+        """(c_in, c_skip, c_out, weight): one fp32 CPU value per entry of `sigmas` (any shape, flattened), each the fp32 tensor
+        expression the training objective evaluates - `_c_in` / `_c_skip_out` (precondition_inputs / _outputs; `v_prediction` flips
+        c_out) and the loss weight (sigma^2 + 0.5^2) / (sigma * 0.5)^2, whose literal 0.5 is the reference's (train_AR.py:975-977),
+        not `sigma_data`"""
+        sigma = torch.as_tensor(sigmas).detach().to("cpu", torch.float32).reshape(-1)
+        c_skip, c_out = self._c_skip_out(sigma)
+        weight = (sigma**2 + 0.5**2) / (sigma * 0.5) ** 2
+        return self._c_in(sigma), c_skip, c_out, weight
+
     def precondition_inputs(self, sample, sigma):
         out = torch.empty_like(sample)
+        if _per_sample(sigma, sample):  # one sigma per sample (the training objective): one launch for the batch
+            c_in = self.edm_coefficients(sigma)[0]
+            hip.edm_noise_inputs(_f32_dev(sample), None, None, hip.upload_nonblocking(c_in, sample.device), None, out)
+            return out
         hip.scale_f32(_f32_dev(sample), float(self._c_in(_host_scalar(sigma))), out)
         return out
 
     def precondition_outputs(self, sample, model_output, sigma):
+        if _per_sample(sigma, sample):  # sample / model_output may be slices along T (push-forward conditions on a slice)
+            _, c_skip, c_out, _ = self.edm_coefficients(sigma)
+            out = torch.empty(sample.shape, device=sample.device, dtype=torch.float32)
+            hip.edm_denoise(sample, model_output, hip.upload_nonblocking(c_skip, sample.device), hip.upload_nonblocking(c_out, sample.device), out)
+            return out
         c_skip, c_out = self._c_skip_out(_host_scalar(sigma))
         out = torch.empty_like(sample)
         hip.axpby_f32(_f32_dev(sample), float(c_skip), _f32_dev(model_output), float(c_out), out)
@@ -189,11 +209,13 @@ class EDMDPMSolverMultistepScheduler:
         return SimpleNamespace(prev_sample=prev)
 
     def add_noise(self, original_samples, noise, timesteps):
-        """x0 + sigma(t) * noise, one sigma per sample (train_AR.py:911; not on the inference path)."""
+        """x0 + sigma(t) * noise, one sigma per sample (train_AR.py:911; not on the inference path): one launch for the batch"""
+        sched = self.timesteps.cpu()
+        sigma = torch.stack([self.sigmas[self.index_for_timestep(t, sched)] for t in timesteps.cpu()]).to(torch.float32)
+        if sigma.numel() != original_samples.shape[0]:
+            raise ValueError(f"add_noise: {sigma.numel()} timesteps for {original_samples.shape[0]} samples")
         out = torch.empty_like(original_samples)
-        for j, t in enumerate(timesteps):
-            sigma = float(self.sigmas[self.index_for_timestep(t.cpu(), self.timesteps.cpu())])
-            hip.axpby_f32(_f32_dev(original_samples[j]), 1.0, _f32_dev(noise[j]), sigma, out[j])
+        hip.edm_noise_inputs(_f32_dev(original_samples), _f32_dev(noise), hip.upload_nonblocking(sigma, original_samples.device), None, out, None)
         return out
 
     def __len__(self):
@@ -216,6 +238,16 @@ def _host_scalar(sigma):
     if isinstance(sigma, torch.Tensor):
         return sigma.detach().to("cpu", torch.float32).reshape(())
     return torch.tensor(float(sigma), dtype=torch.float32)
+
+
+def _per_sample(sigma, sample):
+    """True: `sigma` is a tensor with one entry per sample of a batch of more than one (trailing singleton dims allowed).  A scalar, a
+    0-dim or a one-element tensor takes the scalar path."""
+    if not isinstance(sigma, torch.Tensor) or sigma.numel() == 1:
+        return False
+    if sigma.numel() != sample.shape[0] or sigma.shape[0] != sample.shape[0]:
+        raise ValueError(f"sigma must be a scalar or hold one value per sample: got shape {tuple(sigma.shape)} for a batch of {sample.shape[0]}")
+    return True
 
 
 def _f32_dev(t):
