@@ -580,6 +580,28 @@ int ldc_validation_scores(const float* forecast, long long member_stride, long l
                           const float* mean, const float* std_, float target_std, const float* truth, long long truth_slot_stride,
                           long long truth_channel_stride, const int* truth_slot, const float* lat_weight, int M, int C, int L, int H,
                           int W, float* out, int L_total, int l_off, void* workspace, long long workspace_bytes, void* stream);
+/* Ensemble reliability for every lead time of a decode batch in one launch (additive under ABI 5; reliability.hip):
+ * spread-skill ratio and rank histogram.  Not in the reference.  Addressing of forecast, inverse normalisation, truth table, lat_weight,
+ * out columns and nan_channel exactly as ldc_rollout_scores; no climatology.  There is no sort, so 1 <= M <= 1024.
+ * Per point, members x_i in member order: mean = sum_i x_i / M, se = (mean - t)^2, var = sum_i (x_i - mean)^2 / (M - 1) (two-pass;
+ * M == 1: NaN), rank bin = #{x_i < t} + (#{x_i == t} >> 1) in 0 .. M (ties: deterministic mid-rank).  A point is valid for the histogram
+ * when no member and not the truth is NaN; +-inf are ordinary ordered values.
+ *   out [3][C][L_total] = ens_mse = <w se>, ens_var = <w var>, ssr = sqrt((M + 1) / M) * sqrt(ens_var / ens_mse); each average is a plain
+ *     mean (one NaN point -> NaN) except in channel nan_channel (nanmean over the points where the value is not NaN).  For M <= 64 ens_mse
+ *     holds the bits of ldc_rollout_scores' ens_mse.
+ *   hist_count  [C][L_total][M + 1] int32: valid points per rank bin
+ *   hist_weight [C][L_total][M + 1] fp32: sum of w over the valid points per bin, in a fixed order
+ *   n_invalid   [C][L_total] int32: points left out of the histogram
+ *   Columns l_off .. l_off + L - 1 of every output are written, the others left alone.  No float atomics: run-to-run bit-equal.
+ * workspace: ldc_rollout_reliability_workspace_bytes(M, C, L, H, W) bytes of device scratch (0 for arguments the call refuses).
+ * LDC_ERR_ARG: a null or non-positive argument (M <= 0 among them), a workspace that is too small, or l_off + L > L_total;
+ * LDC_ERR_UNSUPPORTED: M > 1024, C > 65535, L > 65535 or H * W > 2^24.  Nothing is launched on an error. */
+long long ldc_rollout_reliability_workspace_bytes(int M, int C, int L, int H, int W);
+int ldc_rollout_reliability(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride,
+                            const float* mean, const float* std_, float target_std, const float* truth, long long truth_slot_stride,
+                            long long truth_channel_stride, const int* truth_slot, const float* lat_weight, int M, int C, int L, int H,
+                            int W, int nan_channel, float* out, int* hist_count, float* hist_weight, int* n_invalid, int L_total,
+                            int l_off, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

@@ -12,7 +12,8 @@ copy.  Decoded fields never exist beyond one decode batch (the reference keeps t
 
 xarray / zarr are not available: `--data_path` is a .npy of raw frames (N, C, H_in, W), `--step_size_hour` apart, the first at
 `--start_date`; `--climatology_path` a .npy (366, 4, C, H_in, W) (day of year, hour 0 / 6 / 12 / 18).  `H_in == H + 1` crops row 0,
-the south pole.  Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
+the south pole.  `--reliability` adds the spread-skill ratio and the rank histogram (`ldc_rollout_reliability`, not in the reference):
+`ens_var.npy`, `ssr.npy`, `n_invalid.npy` (init time, C, lead time) and `rank_hist.npy`, `rank_hist_weighted.npy` (C, lead time, ens + 1).  Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
 members and the reference's commented-out `single_mse` are out of scope.
 """
 from __future__ import annotations
@@ -28,10 +29,11 @@ import numpy as np
 import torch
 
 from .track import VARIABLE_NAMES, mean_std_from_json
-from .utils import SCORE_NAMES, get_normalized_lat_weights_based_on_cos, rollout_scores
+from .utils import SCORE_NAMES, empty_reliability, get_normalized_lat_weights_based_on_cos, rollout_reliability, rollout_scores
 
 SST_CHANNEL_IDX = 82
 CLIMATOLOGY_HOURS = (0, 6, 12, 18)
+RELIABILITY_KEYS = ("ens_var", "ssr", "rank_hist", "rank_hist_weighted", "n_invalid")  # what `--reliability` adds
 
 
 def _to_datetime(t) -> datetime:
@@ -89,7 +91,7 @@ def _stage_planes(table, slots: Sequence[int], dev, what: str):
 def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model, mean_tensor, std_tensor, truth, truth_slots: Sequence[int],
                          clim, clim_slots: Optional[Sequence[int]], lat_weight: torch.Tensor, *, sst_channel: int = SST_CHANNEL_IDX,
                          total_num_steps: Optional[int] = None, crop_init: bool = False, force_ens_size: Optional[int] = None,
-                         decode_batch_frames: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                         decode_batch_frames: Optional[int] = None, reliability: bool = False) -> Dict[str, torch.Tensor]:
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -99,7 +101,11 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     tables in physical units of which lead t reads entry `truth_slots[t]` / `clim_slots[t]` (clim None: no ACC).  On the device they
     are indexed where they are; host arrays or memmaps have only the planes this initial time needs staged to the device.  Columns
     T .. total_num_steps - 1 stay NaN, as the reference's `torch.full(nan)` leaves them; T > total_num_steps is a ValueError (the
-    reference fails with an index error).  `crop_init` drops slot 0 (the IC latent), `force_ens_size` keeps the first members."""
+    reference fails with an index error).  `crop_init` drops slot 0 (the IC latent), `force_ens_size` keeps the first members.
+
+    `reliability`: every decode batch also goes through `ldc_rollout_reliability` while it is on the device (nothing more is decoded or
+    kept) and the result gains `RELIABILITY_KEYS`: `ens_var`, `ssr` (C, total_num_steps) fp32, `rank_hist` (C, total_num_steps, ens + 1)
+    int32, `rank_hist_weighted` the same in fp32, `n_invalid` (C, total_num_steps) int32; the five scores are the bits of a call without it."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
 
@@ -133,7 +139,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     lat_weight = lat_weight.to(dev, torch.float32)
     latents = latents.to(dev, torch.float32)
     per = max(1, int(decode_batch_frames) // ens) if decode_batch_frames else 1  # lead times per decoder call: a lead time's members stay together
-    scores = None
+    scores = rel = None
     for s0 in range(0, T, per):
         nl = min(per, T - s0)
         x = latents[:, :, s0 : s0 + nl].permute(2, 0, 1, 3, 4).reshape(nl * ens, C, h, w).contiguous()  # lead-major, then member
@@ -142,8 +148,16 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             scores = torch.full((5, y.shape[1], total), float("nan"), device=dev, dtype=torch.float32)
         rollout_scores(y.reshape(nl, ens, *y.shape[1:]), truth, clim, lat_weight, sst_channel, lead_dim=0, mean=mean_d, std=std_d,
                        truth_slots=t_slots[s0 : s0 + nl], clim_slots=None if clim is None else c_slots[s0 : s0 + nl], out=scores, lead_offset=s0)
+        if reliability:
+            if rel is None:
+                rel = empty_reliability(ens, y.shape[1], total, dev)
+            rollout_reliability(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, sst_channel, lead_dim=0, mean=mean_d, std=std_d,
+                                truth_slot=t_slots[s0 : s0 + nl], out=rel, l_off=s0)
     host = scores.cpu()  # the one copy (and the one wait) of this initial time
-    return {k: host[i] for i, k in enumerate(SCORE_NAMES)}
+    res = {k: host[i] for i, k in enumerate(SCORE_NAMES)}
+    if reliability:
+        res.update({k: rel[k].cpu() for k in RELIABILITY_KEYS})
+    return res
 
 
 def lat_weights_for(H: int) -> torch.Tensor:
@@ -179,9 +193,37 @@ def _crop_rows(table: np.ndarray, H: int, what: str) -> np.ndarray:
     return table
 
 
+def _gather_reliability(rel: dict, res, time_str: str, total_num_steps: int) -> None:
+    """one initial time's `RELIABILITY_KEYS` into the run's: `ens_var`, `ssr` (fp32) and `n_invalid` (int32) are kept per initial time,
+    the rank histograms are summed over the initial times on the host - the counts in int64, the weighted ones in float64"""
+    missing = [k for k in RELIABILITY_KEYS if k not in res]
+    if missing:
+        raise ValueError(f"{time_str}: --reliability needs {missing} from the scorer")
+    a = {k: np.asarray(res[k]) for k in RELIABILITY_KEYS}
+    C = a["ens_var"].shape[0]
+    hist_shape = a["rank_hist"].shape
+    if any(a[k].shape != (C, total_num_steps) for k in ("ens_var", "ssr", "n_invalid")) or len(hist_shape) != 3 \
+            or hist_shape[:2] != (C, total_num_steps) or a["rank_hist_weighted"].shape != hist_shape:
+        raise ValueError(f"{time_str}: reliability arrays of shapes { {k: v.shape for k, v in a.items()} }, expected (C, {total_num_steps}) "
+                         f"and (C, {total_num_steps}, members + 1)")
+    if rel["rank_hist"] is None:
+        rel["rank_hist"], rel["rank_hist_weighted"] = np.zeros(hist_shape, dtype=np.int64), np.zeros(hist_shape, dtype=np.float64)
+    elif rel["rank_hist"].shape != hist_shape:
+        raise ValueError(f"{time_str}: a rank histogram of {hist_shape[2] - 1} members after one of {rel['rank_hist'].shape[2] - 1}")
+    rel["ens_var"].append(a["ens_var"].astype(np.float32))
+    rel["ssr"].append(a["ssr"].astype(np.float32))
+    rel["n_invalid"].append(a["n_invalid"].astype(np.int32))
+    rel["rank_hist"] += a["rank_hist"].astype(np.int64)
+    rel["rank_hist_weighted"] += a["rank_hist_weighted"].astype(np.float64)
+
+
 def main(argv=None, score: Optional[Callable] = None):
     """`score(path, time_str, truth_slots, clim_slots) -> {name: (C, total_num_steps)}` replaces the autoencoder, the data and the device
     (tests of the file handling).  Returns the gathered arrays, `timestamp` among them.
+
+    `--reliability` (the scorer then returns `RELIABILITY_KEYS` too) adds `ens_var.npy`, `ssr.npy` (init time, C, lead time) fp32,
+    `n_invalid.npy` the same in int32, and the rank histograms summed over the initial times: `rank_hist.npy` (C, lead time, members + 1)
+    int64 and `rank_hist_weighted.npy` float64.  Without it the launches and the files are those of a run before the flag existed.
 
     `timestamp.npy` is float32, as the reference stores it: YYYYMMDDHH does not fit fp32's 24 bits, e.g. 2018123118 reads back as
     2018123136.  The per-time file names carry the exact time."""
@@ -204,6 +246,7 @@ def main(argv=None, score: Optional[Callable] = None):
     ap.add_argument("--sst_channel_idx", type=int, default=SST_CHANNEL_IDX, help="the channel averaged with nanmean (NaN over land)")
     ap.add_argument("--variable_names", nargs="+", default=VARIABLE_NAMES, help="variables of the normalisation JSON, in channel order")
     ap.add_argument("--gemm_precision", type=str, default="fp32", choices=("fp32", "bf16x3", "bf16"))
+    ap.add_argument("--reliability", action="store_true", help="also write ens_var, ssr, rank_hist, rank_hist_weighted and n_invalid")
     args = ap.parse_args(argv)
 
     if args.total_lead_time_hour % args.step_size_hour != 0:
@@ -241,10 +284,11 @@ def main(argv=None, score: Optional[Callable] = None):
         def score(path, time_str, t_slots, c_slots):
             return score_latent_rollout(path, model, mean_t, std_t, truth, t_slots, clim, c_slots, lat_w, sst_channel=args.sst_channel_idx,
                                         total_num_steps=total_num_steps, crop_init=args.crop_init, force_ens_size=args.force_ens_size,
-                                        decode_batch_frames=args.decode_batch_frames)
+                                        decode_batch_frames=args.decode_batch_frames, reliability=args.reliability)
 
     os.makedirs(args.output, exist_ok=True)
     gathered = {k: [] for k in SCORE_NAMES}
+    rel = dict(ens_var=[], ssr=[], n_invalid=[], rank_hist=None, rank_hist_weighted=None)
     for i, (time_str, path) in enumerate(files):
         print(f"processing time_str: {time_str}, remaining: {len(files) - i - 1}")
         init = _to_datetime(int(time_str))
@@ -256,7 +300,11 @@ def main(argv=None, score: Optional[Callable] = None):
                 raise ValueError(f"{time_str}: {k} is {a.shape}, expected (C, {total_num_steps})")
             np.save(os.path.join(args.output, f"{time_str}_{k}.npy"), a)
             gathered[k].append(a)
+        if args.reliability:
+            _gather_reliability(rel, res, time_str, total_num_steps)
     out = {k: np.stack(v) for k, v in gathered.items()}
+    if args.reliability:
+        out.update({k: np.stack(rel[k]) for k in ("ens_var", "ssr", "n_invalid")}, rank_hist=rel["rank_hist"], rank_hist_weighted=rel["rank_hist_weighted"])
     out["timestamp"] = np.array([int(t) for t, _ in files]).astype(np.float32)  # as the reference: a float32 tensor of YYYYMMDDHH
     for k, a in out.items():
         np.save(os.path.join(args.output, f"{k}.npy"), a)

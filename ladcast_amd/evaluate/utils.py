@@ -238,3 +238,81 @@ def validation_scores(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: t
                           channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
                           target_std=target_std, L_total=buf.shape[2], l_off=lead_offset)
     return ScoreDict(buf, VALIDATION_SCORE_NAMES)
+
+
+RELIABILITY_NAMES = ("ens_mse", "ens_var", "ssr")  # the planes of ldc_rollout_reliability's `out`, in order
+MAX_RELIABILITY_MEMBERS = 1024
+
+
+class ReliabilityDict(dict):
+    """{ens_mse, ens_var, ssr: (C, L_total) fp32; rank_hist: (C, L_total, M + 1) int32; rank_hist_weighted: the same in fp32;
+    n_invalid: (C, L_total) int32} over the four device buffers `ldc_rollout_reliability` fills"""
+
+    def __init__(self, buf, hist, hist_w, n_invalid):
+        super().__init__({k: buf[i] for i, k in enumerate(RELIABILITY_NAMES)})
+        self.update(rank_hist=hist, rank_hist_weighted=hist_w, n_invalid=n_invalid)
+        self._buffers = (buf, hist, hist_w, n_invalid)
+
+
+def empty_reliability(M: int, C: int, L_total: int, device) -> ReliabilityDict:
+    """the result of `rollout_reliability` before any column is written: scores NaN, histograms and `n_invalid` zero"""
+    n = len(RELIABILITY_NAMES)
+    return ReliabilityDict(torch.full((n, C, L_total), float("nan"), device=device, dtype=torch.float32),
+                           torch.zeros(C, L_total, M + 1, device=device, dtype=torch.int32),
+                           torch.zeros(C, L_total, M + 1, device=device, dtype=torch.float32),
+                           torch.zeros(C, L_total, device=device, dtype=torch.int32))
+
+
+@torch.no_grad()
+def rollout_reliability(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torch.Tensor, sst_channel: int, *, lead_dim: int = 2,
+                        mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, target_std: float = 1.0, truth_slot=None,
+                        out: Optional[Dict[str, torch.Tensor]] = None, l_off: int = 0) -> Dict[str, torch.Tensor]:
+    """Spread-skill ratio and rank histogram of every lead time in one launch (`ldc_rollout_reliability`; not in the reference).  Per
+    grid point with members x_i, truth t: mean = sum_i x_i / M, se = (mean - t)^2, var = sum_i (x_i - mean)^2 / (M - 1) (NaN for one
+    member), rank bin = #{x_i < t} + (#{x_i == t} >> 1): a truth that ties k members takes the deterministic mid-rank.
+        ens_mse = <w se>,  ens_var = <w var>,  ssr = sqrt((M + 1) / M) * sqrt(ens_var / ens_mse)
+    averaged with mean (one NaN point -> NaN), channel `sst_channel` with nanmean.  `rank_hist[c, l, b]` counts the points whose truth has
+    rank b among the members, `rank_hist_weighted` sums their latitude weights, `n_invalid` counts the points left out: those with a NaN
+    member or a NaN truth (+-inf are ordinary ordered values).  1 <= M <= 1024.
+
+    forecast, `lead_dim`, `mean` / `std` / `target_std`: as `rollout_scores`.  truth: (C, L, H, W), or with `truth_slot` (one host int
+    per lead time) an (N, C, H, W) table.  Returns a dict of device tensors with L_total = l_off + L columns (unwritten columns: NaN, empty
+    histograms), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call returned."""
+    hip._dev(forecast, truth, lat_weight, mean, std)
+    if forecast.dim() != 5 or lead_dim not in (0, 2):
+        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
+    if forecast.dtype != torch.float32:
+        raise NotImplementedError("fp32 only")
+    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
+    M, C, L, H, W = f.shape
+    if not 1 <= M <= MAX_RELIABILITY_MEMBERS:
+        raise ValueError(f"{M} members: ldc_rollout_reliability serves 1 .. {MAX_RELIABILITY_MEMBERS}")
+    if f.stride(-1) != 1 or f.stride(-2) != W:
+        f = f.contiguous()
+    dev = f.device
+    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
+    w = lat_weight.to(dev, torch.float32).reshape(-1).contiguous()
+    if w.numel() != H:
+        raise ValueError("lat_weight must have one value per latitude row")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
+        if mean.numel() != C or std.numel() != C:
+            raise ValueError(f"mean / std must hold one value per channel ({C})")
+    n = len(RELIABILITY_NAMES)
+    if out is None:
+        bufs = empty_reliability(M, C, l_off + L, dev)._buffers
+    else:
+        bufs = getattr(out, "_buffers", None)
+        ok = bufs is not None and bufs[0].dim() == 3 and bufs[0].shape[:2] == (n, C) and all(b.is_contiguous() and b.device == dev for b in bufs)
+        if ok:
+            Lt = bufs[0].shape[2]
+            ok = bufs[1].shape == (C, Lt, M + 1) and bufs[2].shape == (C, Lt, M + 1) and bufs[3].shape == (C, Lt)
+        if not ok:
+            raise ValueError("out must be the dict an earlier rollout_reliability call returned for the same ensemble size and channels")
+    slots = hip.upload_nonblocking(torch.tensor(t_slots, dtype=torch.int32), dev)
+    hip.rollout_reliability(f, t, slots, w, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
+                            channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
+                            target_std=target_std, nan_channel=sst_channel, L_total=bufs[0].shape[2], l_off=l_off)
+    return ReliabilityDict(*bufs)
