@@ -602,6 +602,35 @@ int ldc_rollout_reliability(const float* forecast, long long member_stride, long
                             long long truth_channel_stride, const int* truth_slot, const float* lat_weight, int M, int C, int L, int H,
                             int W, int nan_channel, float* out, int* hist_count, float* hist_weight, int* n_invalid, int L_total,
                             int l_off, void* workspace, long long workspace_bytes, void* stream);
+/* Zonal power spectra for every lead time of a decode batch in one launch (additive under ABI 5; spectrum.hip):
+ * power per longitudinal wavenumber of the members, of the ensemble mean and of the truth.  Not in the reference.  Addressing of
+ * forecast, inverse normalisation (mean == NULL: physical units), truth table and out columns exactly as ldc_rollout_reliability; no
+ * climatology and no nan_channel.  row_weight [H] fp32 on the device replaces the latitude weight and must be >= 0 (the call cannot
+ * check device memory: a negative or NaN weight is treated as 0).  A row of weight 0 is not read: NaN or inf there has no effect.
+ * Definitions, per row of W points with positive weight, x_i the de-normalised members, t the truth, m_j = (sum_i x_ij) / M summed in
+ * member order in fp32 (as ldc_rollout_reliability), K = W / 2 + 1, and for a real sequence y:
+ *     Y_k = sum_j y_j exp(-2 pi i j k / W),  P_k(y) = s_k |Y_k|^2 / W^2,  s_0 = s_{W/2} = 1, s_k = 2 otherwise: sum_k P_k = mean_j y_j^2
+ *   P_0 is the square of the row mean (pair sums in index order, then a butterfly); the bins k >= 1 are transformed from the residual
+ *   y_j - mean, folded by the real-input symmetry, with twiddles from one W-entry table per launch (fp64 sincospi rounded to fp32) and
+ *   explicit fused multiply-adds in index order; |Y_k|^2 and every sum over members and rows are fp64.
+ * Validity: a row is valid when none of its (M + 1) W member and truth values is NaN after the inverse normalisation; +-inf are
+ *   ordinary values (they give inf or NaN power).  Invalid rows are left out of every average and counted.
+ *   out [3][C][L_total][K] fp32 = spec_members = <(1 / M) sum_i P_k(x_i)>, spec_mean = <P_k(m)>, spec_truth = <P_k(t)>, with
+ *     <.> = sum_h w_h (.) / sum_h w_h over the valid rows of that (c, l); no valid row: NaN in all 3 K values.  At M == 1 spec_members
+ *     and spec_mean are equal bit for bit.
+ *   n_invalid [C][L_total] int32: rows of positive weight left out.
+ *   Columns l_off .. l_off + L - 1 of both outputs are written, the others left alone.  No atomics: run-to-run bit-equal.
+ * workspace: ldc_rollout_spectrum_workspace_bytes(M, C, L, H, W) bytes of device scratch, 16-byte aligned (0 for arguments the call
+ *   refuses).
+ * LDC_ERR_ARG: a null or non-positive argument, l_off + L > L_total or a workspace that is too small; LDC_ERR_UNSUPPORTED: M > 1024,
+ * W odd, W < 4, W > 512, H * W > 2^24, C > 65535 or L > 65535; LDC_ERR_ALIGN: workspace not 16-byte aligned.  Nothing is launched on
+ * an error. */
+long long ldc_rollout_spectrum_workspace_bytes(int M, int C, int L, int H, int W);
+int ldc_rollout_spectrum(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride,
+                         const float* mean, const float* std_, float target_std, const float* truth, long long truth_slot_stride,
+                         long long truth_channel_stride, const int* truth_slot, const float* row_weight, int M, int C, int L, int H,
+                         int W, float* out, int* n_invalid, int L_total, int l_off, void* workspace, long long workspace_bytes,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

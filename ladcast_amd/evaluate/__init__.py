@@ -1,11 +1,11 @@
 from .utils import (VALIDATION_SCORE_NAMES, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
-                    get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_reliability, rollout_scores, validation_scores)
+                    get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_reliability, rollout_scores, rollout_spectrum, validation_scores)
 
 _DRIVER_NAMES = ("climatology_slots", "score_latent_rollout", "truth_frame_slots")  # evaluate_ens_gpu's, resolved at first use: the
 _VALIDATE_NAMES = ("NpyLatentStore", "log_validation", "validate_initial_time")  # validate_AR's, likewise
 _DENOISE_NAMES = ("denoising_loss", "evaluate_denoising_loss", "push_forward_plan")  # denoise_loss's, likewise
 __all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
-           "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores",  # also runs
+           "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores", "rollout_spectrum",  # also runs
            "validation_scores", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES]  # as `python -m`
 
 

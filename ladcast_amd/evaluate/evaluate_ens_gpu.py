@@ -13,7 +13,10 @@ copy.  Decoded fields never exist beyond one decode batch (the reference keeps t
 xarray / zarr are not available: `--data_path` is a .npy of raw frames (N, C, H_in, W), `--step_size_hour` apart, the first at
 `--start_date`; `--climatology_path` a .npy (366, 4, C, H_in, W) (day of year, hour 0 / 6 / 12 / 18).  `H_in == H + 1` crops row 0,
 the south pole.  `--reliability` adds the spread-skill ratio and the rank histogram (`ldc_rollout_reliability`, not in the reference):
-`ens_var.npy`, `ssr.npy`, `n_invalid.npy` (init time, C, lead time) and `rank_hist.npy`, `rank_hist_weighted.npy` (C, lead time, ens + 1).  Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
+`ens_var.npy`, `ssr.npy`, `n_invalid.npy` (init time, C, lead time) and `rank_hist.npy`, `rank_hist_weighted.npy` (C, lead time, ens + 1).  `--spectrum` adds the zonal power spectra of the members, the ensemble
+mean and the truth (`ldc_rollout_spectrum`, not in the reference): `spec_members.npy`, `spec_mean.npy`, `spec_truth.npy` (init time, C,
+lead time, W / 2 + 1) and `spec_n_invalid.npy` (init time, C, lead time); `--spectrum_lat_band LO HI` keeps the rows between two latitudes.
+Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
 members and the reference's commented-out `single_mse` are out of scope.
 """
 from __future__ import annotations
@@ -29,11 +32,13 @@ import numpy as np
 import torch
 
 from .track import VARIABLE_NAMES, mean_std_from_json
-from .utils import SCORE_NAMES, empty_reliability, get_normalized_lat_weights_based_on_cos, rollout_reliability, rollout_scores
+from .utils import (SCORE_NAMES, SPECTRUM_NAMES, empty_reliability, empty_spectrum, get_normalized_lat_weights_based_on_cos, rollout_reliability,
+                    rollout_scores, rollout_spectrum)
 
 SST_CHANNEL_IDX = 82
 CLIMATOLOGY_HOURS = (0, 6, 12, 18)
 RELIABILITY_KEYS = ("ens_var", "ssr", "rank_hist", "rank_hist_weighted", "n_invalid")  # what `--reliability` adds
+SPECTRUM_KEYS = SPECTRUM_NAMES + ("spec_n_invalid",)  # what `--spectrum` adds
 
 
 def _to_datetime(t) -> datetime:
@@ -91,7 +96,8 @@ def _stage_planes(table, slots: Sequence[int], dev, what: str):
 def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model, mean_tensor, std_tensor, truth, truth_slots: Sequence[int],
                          clim, clim_slots: Optional[Sequence[int]], lat_weight: torch.Tensor, *, sst_channel: int = SST_CHANNEL_IDX,
                          total_num_steps: Optional[int] = None, crop_init: bool = False, force_ens_size: Optional[int] = None,
-                         decode_batch_frames: Optional[int] = None, reliability: bool = False) -> Dict[str, torch.Tensor]:
+                         decode_batch_frames: Optional[int] = None, reliability: bool = False, spectrum: bool = False,
+                         spectrum_row_weight: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -105,7 +111,12 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
 
     `reliability`: every decode batch also goes through `ldc_rollout_reliability` while it is on the device (nothing more is decoded or
     kept) and the result gains `RELIABILITY_KEYS`: `ens_var`, `ssr` (C, total_num_steps) fp32, `rank_hist` (C, total_num_steps, ens + 1)
-    int32, `rank_hist_weighted` the same in fp32, `n_invalid` (C, total_num_steps) int32; the five scores are the bits of a call without it."""
+    int32, `rank_hist_weighted` the same in fp32, `n_invalid` (C, total_num_steps) int32; the five scores are the bits of a call without it.
+
+    `spectrum`: every decode batch also goes through `ldc_rollout_spectrum` while it is on the device and the result gains
+    `SPECTRUM_KEYS`: `spec_members`, `spec_mean`, `spec_truth` (C, total_num_steps, W / 2 + 1) fp32 and `spec_n_invalid` (C, total_num_steps)
+    int32.  `spectrum_row_weight` (H,), non-negative, weights the rows (0: the row is left out and never read); default: `lat_weight`.  The
+    five scores and the reliability outputs are the bits of a call without it."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
 
@@ -138,8 +149,13 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     mean_d, std_d = _device_vector(mean_tensor, dev), _device_vector(std_tensor, dev)
     lat_weight = lat_weight.to(dev, torch.float32)
     latents = latents.to(dev, torch.float32)
+    if spectrum:
+        spec_w = lat_weight if spectrum_row_weight is None else spectrum_row_weight
+        if not spec_w.is_cuda and not bool((spec_w >= 0).all()):
+            raise ValueError("spectrum_row_weight must be non-negative (0 leaves a row out) and not NaN")
+        spec_w = spec_w.to(dev, torch.float32)
     per = max(1, int(decode_batch_frames) // ens) if decode_batch_frames else 1  # lead times per decoder call: a lead time's members stay together
-    scores = rel = None
+    scores = rel = spec = None
     for s0 in range(0, T, per):
         nl = min(per, T - s0)
         x = latents[:, :, s0 : s0 + nl].permute(2, 0, 1, 3, 4).reshape(nl * ens, C, h, w).contiguous()  # lead-major, then member
@@ -153,10 +169,17 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                 rel = empty_reliability(ens, y.shape[1], total, dev)
             rollout_reliability(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, sst_channel, lead_dim=0, mean=mean_d, std=std_d,
                                 truth_slot=t_slots[s0 : s0 + nl], out=rel, l_off=s0)
+        if spectrum:
+            if spec is None:
+                spec = empty_spectrum(y.shape[1], total, y.shape[3], dev)
+            rollout_spectrum(y.reshape(nl, ens, *y.shape[1:]), truth, spec_w, lead_dim=0, mean=mean_d, std=std_d,
+                             truth_slot=t_slots[s0 : s0 + nl], out=spec, l_off=s0)
     host = scores.cpu()  # the one copy (and the one wait) of this initial time
     res = {k: host[i] for i, k in enumerate(SCORE_NAMES)}
     if reliability:
         res.update({k: rel[k].cpu() for k in RELIABILITY_KEYS})
+    if spectrum:
+        res.update({k: spec[k].cpu() for k in SPECTRUM_NAMES}, spec_n_invalid=spec["n_invalid"].cpu())
     return res
 
 
@@ -217,6 +240,41 @@ def _gather_reliability(rel: dict, res, time_str: str, total_num_steps: int) -> 
     rel["rank_hist_weighted"] += a["rank_hist_weighted"].astype(np.float64)
 
 
+def _gather_spectrum(spec: dict, res, time_str: str, total_num_steps: int) -> None:
+    """one initial time's `SPECTRUM_KEYS` into the run's: kept per initial time, the spectra in fp32, `spec_n_invalid` in int32"""
+    missing = [k for k in SPECTRUM_KEYS if k not in res]
+    if missing:
+        raise ValueError(f"{time_str}: --spectrum needs {missing} from the scorer")
+    a = {k: np.asarray(res[k]) for k in SPECTRUM_KEYS}
+    shape = a[SPECTRUM_NAMES[0]].shape
+    if len(shape) != 3 or shape[1] != total_num_steps or any(a[k].shape != shape for k in SPECTRUM_NAMES) or a["spec_n_invalid"].shape != shape[:2]:
+        raise ValueError(f"{time_str}: spectrum arrays of shapes { {k: v.shape for k, v in a.items()} }, expected (C, {total_num_steps}, K) "
+                         f"and (C, {total_num_steps})")
+    for k in SPECTRUM_NAMES:
+        spec[k].append(a[k].astype(np.float32))
+    spec["spec_n_invalid"].append(a["spec_n_invalid"].astype(np.int32))
+
+
+def spectrum_band_weights(lat_weight: torch.Tensor, lat_deg, band) -> torch.Tensor:
+    """`lat_weight` (H,) with the rows whose latitude `lat_deg` (H,) lies outside [band[0], band[1]] degrees set to 0; band None: unchanged"""
+    if band is None:
+        return lat_weight
+    lo, hi = float(band[0]), float(band[1])
+    if not lo <= hi:
+        raise ValueError(f"--spectrum_lat_band {lo} {hi}: LO must not exceed HI")
+    lat = torch.as_tensor(np.asarray(lat_deg, dtype=np.float64))
+    inside = (lat >= lo) & (lat <= hi)
+    if not bool(inside.any()):
+        raise ValueError(f"--spectrum_lat_band {lo} {hi}: no latitude row inside (rows from {float(lat.min())} to {float(lat.max())})")
+    return torch.where(inside, lat_weight, torch.zeros_like(lat_weight))
+
+
+def row_latitudes(H: int) -> np.ndarray:
+    """the latitudes in degrees of the H rows `lat_weights_for` weighs: the 120-row grid's, else the H rows kept of an equiangular
+    pole-to-pole grid of H + 1 (row 0, the south pole, dropped)"""
+    return np.linspace(-88.5, 90, 120) if H == 120 else np.linspace(-90.0, 90.0, H + 1)[1:]
+
+
 def main(argv=None, score: Optional[Callable] = None):
     """`score(path, time_str, truth_slots, clim_slots) -> {name: (C, total_num_steps)}` replaces the autoencoder, the data and the device
     (tests of the file handling).  Returns the gathered arrays, `timestamp` among them.
@@ -224,6 +282,10 @@ def main(argv=None, score: Optional[Callable] = None):
     `--reliability` (the scorer then returns `RELIABILITY_KEYS` too) adds `ens_var.npy`, `ssr.npy` (init time, C, lead time) fp32,
     `n_invalid.npy` the same in int32, and the rank histograms summed over the initial times: `rank_hist.npy` (C, lead time, members + 1)
     int64 and `rank_hist_weighted.npy` float64.  Without it the launches and the files are those of a run before the flag existed.
+
+    `--spectrum` (the scorer then returns `SPECTRUM_KEYS` too) adds `spec_members.npy`, `spec_mean.npy`, `spec_truth.npy` (init time, C,
+    lead time, W / 2 + 1) fp32 and `spec_n_invalid.npy` (init time, C, lead time) int32; `--spectrum_lat_band LO HI` (degrees) gives the
+    rows outside the band weight 0, the rows inside keep the cos weight.
 
     `timestamp.npy` is float32, as the reference stores it: YYYYMMDDHH does not fit fp32's 24 bits, e.g. 2018123118 reads back as
     2018123136.  The per-time file names carry the exact time."""
@@ -247,6 +309,9 @@ def main(argv=None, score: Optional[Callable] = None):
     ap.add_argument("--variable_names", nargs="+", default=VARIABLE_NAMES, help="variables of the normalisation JSON, in channel order")
     ap.add_argument("--gemm_precision", type=str, default="fp32", choices=("fp32", "bf16x3", "bf16"))
     ap.add_argument("--reliability", action="store_true", help="also write ens_var, ssr, rank_hist, rank_hist_weighted and n_invalid")
+    ap.add_argument("--spectrum", action="store_true", help="also write spec_members, spec_mean, spec_truth and spec_n_invalid")
+    ap.add_argument("--spectrum_lat_band", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="latitudes in degrees between which rows enter the spectra (default: all rows)")
     args = ap.parse_args(argv)
 
     if args.total_lead_time_hour % args.step_size_hour != 0:
@@ -280,15 +345,18 @@ def main(argv=None, score: Optional[Callable] = None):
             truth = torch.from_numpy(np.ascontiguousarray(truth, dtype=np.float32)).to("cuda")
             clim = torch.from_numpy(np.ascontiguousarray(clim, dtype=np.float32)).to("cuda")
         lat_w = lat_weights_for(H)
+        spec_w = spectrum_band_weights(lat_w, row_latitudes(H), args.spectrum_lat_band) if args.spectrum else None
 
         def score(path, time_str, t_slots, c_slots):
             return score_latent_rollout(path, model, mean_t, std_t, truth, t_slots, clim, c_slots, lat_w, sst_channel=args.sst_channel_idx,
                                         total_num_steps=total_num_steps, crop_init=args.crop_init, force_ens_size=args.force_ens_size,
-                                        decode_batch_frames=args.decode_batch_frames, reliability=args.reliability)
+                                        decode_batch_frames=args.decode_batch_frames, reliability=args.reliability, spectrum=args.spectrum,
+                                        spectrum_row_weight=spec_w)
 
     os.makedirs(args.output, exist_ok=True)
     gathered = {k: [] for k in SCORE_NAMES}
     rel = dict(ens_var=[], ssr=[], n_invalid=[], rank_hist=None, rank_hist_weighted=None)
+    spec = {k: [] for k in SPECTRUM_KEYS}
     for i, (time_str, path) in enumerate(files):
         print(f"processing time_str: {time_str}, remaining: {len(files) - i - 1}")
         init = _to_datetime(int(time_str))
@@ -302,9 +370,13 @@ def main(argv=None, score: Optional[Callable] = None):
             gathered[k].append(a)
         if args.reliability:
             _gather_reliability(rel, res, time_str, total_num_steps)
+        if args.spectrum:
+            _gather_spectrum(spec, res, time_str, total_num_steps)
     out = {k: np.stack(v) for k, v in gathered.items()}
     if args.reliability:
         out.update({k: np.stack(rel[k]) for k in ("ens_var", "ssr", "n_invalid")}, rank_hist=rel["rank_hist"], rank_hist_weighted=rel["rank_hist_weighted"])
+    if args.spectrum:
+        out.update({k: np.stack(v) for k, v in spec.items()})
     out["timestamp"] = np.array([int(t) for t, _ in files]).astype(np.float32)  # as the reference: a float32 tensor of YYYYMMDDHH
     for k, a in out.items():
         np.save(os.path.join(args.output, f"{k}.npy"), a)

@@ -316,3 +316,83 @@ def rollout_reliability(forecast: torch.Tensor, truth: torch.Tensor, lat_weight:
                             channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
                             target_std=target_std, nan_channel=sst_channel, L_total=bufs[0].shape[2], l_off=l_off)
     return ReliabilityDict(*bufs)
+
+
+SPECTRUM_NAMES = ("spec_members", "spec_mean", "spec_truth")  # the planes of ldc_rollout_spectrum's `out`, in order
+MAX_SPECTRUM_MEMBERS = 1024
+MIN_SPECTRUM_W, MAX_SPECTRUM_W = 4, 512
+
+
+class SpectrumDict(dict):
+    """{spec_members, spec_mean, spec_truth: (C, L_total, W / 2 + 1) fp32; n_invalid: (C, L_total) int32} over the two device buffers
+    `ldc_rollout_spectrum` fills"""
+
+    def __init__(self, buf, n_invalid):
+        super().__init__({k: buf[i] for i, k in enumerate(SPECTRUM_NAMES)})
+        self.update(n_invalid=n_invalid)
+        self._buffers = (buf, n_invalid)
+
+
+def empty_spectrum(C: int, L_total: int, W: int, device) -> SpectrumDict:
+    """the result of `rollout_spectrum` before any column is written: spectra NaN, `n_invalid` zero"""
+    return SpectrumDict(torch.full((len(SPECTRUM_NAMES), C, L_total, W // 2 + 1), float("nan"), device=device, dtype=torch.float32),
+                        torch.zeros(C, L_total, device=device, dtype=torch.int32))
+
+
+@torch.no_grad()
+def rollout_spectrum(forecast: torch.Tensor, truth: torch.Tensor, row_weight: torch.Tensor, *, lead_dim: int = 2,
+                     mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, target_std: float = 1.0, truth_slot=None,
+                     out: Optional[Dict[str, torch.Tensor]] = None, l_off: int = 0) -> Dict[str, torch.Tensor]:
+    """Zonal power spectra of every lead time in one launch (`ldc_rollout_spectrum`; not in the reference).  Per latitude row of W points,
+    for a real sequence y: Y_k = sum_j y_j exp(-2 pi i j k / W), P_k(y) = s_k |Y_k|^2 / W^2 for k = 0 .. W / 2 (s_k = 1 at k = 0 and W / 2,
+    2 otherwise), so that sum_k P_k(y) = mean_j y_j^2.  With members x_i, truth t and the ensemble mean m = sum_i x_i / M:
+        spec_members = <(1 / M) sum_i P_k(x_i)>,  spec_mean = <P_k(m)>,  spec_truth = <P_k(t)>,   <.> = sum_h w_h (.) / sum_h w_h
+    over the rows h of positive `row_weight` that hold no NaN among their members and truth; `n_invalid` counts the rows of positive
+    weight left out, and a (channel, lead time) without a valid row is NaN.  A row of weight 0 is not read: this is how a latitude band
+    is selected.  The row mean is removed before the transform (P_0 is its square), so a field's large mean puts no noise floor under
+    the bins k >= 1.  1 <= M <= 1024; W even, 4 <= W <= 512.
+
+    `row_weight` (H,): non-negative.  A host tensor is checked here (ValueError for a negative or NaN weight); a device tensor is the
+    caller's responsibility: the kernel treats a weight that is not > 0 as 0.  forecast, `lead_dim`, `mean` / `std` / `target_std`, truth /
+    `truth_slot`, `out` / `l_off`: as `rollout_reliability`.  Returns a dict of device tensors with L_total = l_off + L columns (unwritten
+    columns: NaN, `n_invalid` 0), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_spectrum`) returned."""
+    if forecast.dim() != 5 or lead_dim not in (0, 2):
+        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
+    if forecast.dtype != torch.float32:
+        raise NotImplementedError("fp32 only")
+    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
+    M, C, L, H, W = f.shape
+    if W % 2 or not MIN_SPECTRUM_W <= W <= MAX_SPECTRUM_W:
+        raise ValueError(f"{W} points per row: ldc_rollout_spectrum serves even W in {MIN_SPECTRUM_W} .. {MAX_SPECTRUM_W}")
+    if not 1 <= M <= MAX_SPECTRUM_MEMBERS:
+        raise ValueError(f"{M} members: ldc_rollout_spectrum serves 1 .. {MAX_SPECTRUM_MEMBERS}")
+    if row_weight.numel() != H:
+        raise ValueError("row_weight must have one value per latitude row")
+    if not row_weight.is_cuda and not bool((row_weight >= 0).all()):  # NaN fails the comparison too
+        raise ValueError("row_weight must be non-negative (0 leaves a row out) and not NaN")
+    hip._dev(forecast, truth, mean, std)
+    if f.stride(-1) != 1 or f.stride(-2) != W:
+        f = f.contiguous()
+    dev = f.device
+    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
+    w = row_weight.to(dev, torch.float32).reshape(-1).contiguous()
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
+        if mean.numel() != C or std.numel() != C:
+            raise ValueError(f"mean / std must hold one value per channel ({C})")
+    n, K = len(SPECTRUM_NAMES), W // 2 + 1
+    if out is None:
+        bufs = empty_spectrum(C, l_off + L, W, dev)._buffers
+    else:
+        bufs = getattr(out, "_buffers", None)
+        ok = bufs is not None and len(bufs) == 2 and bufs[0].dim() == 4 and bufs[0].shape[:2] == (n, C) and bufs[0].shape[3] == K \
+            and bufs[0].dtype == torch.float32 and bufs[1].dtype == torch.int32 and all(b.is_contiguous() and b.device == dev for b in bufs)
+        if not (ok and bufs[1].shape == (C, bufs[0].shape[2])):
+            raise ValueError("out must be the dict an earlier rollout_spectrum call (or empty_spectrum) returned for the same channels and W")
+    slots = hip.upload_nonblocking(torch.tensor(t_slots, dtype=torch.int32), dev)
+    hip.rollout_spectrum(f, t, slots, w, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
+                         channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
+                         target_std=target_std, L_total=bufs[0].shape[2], l_off=l_off)
+    return SpectrumDict(*bufs)

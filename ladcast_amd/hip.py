@@ -110,6 +110,8 @@ def _load():
         "ldc_validation_scores": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, P, I, I, P, L, P]),
         "ldc_rollout_reliability_workspace_bytes": (L, [I, I, I, I, I]),
         "ldc_rollout_reliability": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, L, P]),
+        "ldc_rollout_spectrum_workspace_bytes": (L, [I, I, I, I, I]),
+        "ldc_rollout_spectrum": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, P, P, I, I, P, L, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
         "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
         "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
@@ -413,6 +415,18 @@ def rollout_reliability(forecast, truth, truth_slot, lat_weight, out, hist_count
                                        truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(lat_weight), M, C, L, H, W, nan_channel,
                                        _p(out), _p(hist_count), _p(hist_weight), _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4,
                                        _stream()), "ldc_rollout_reliability")
+
+
+def rollout_spectrum(forecast, truth, truth_slot, row_weight, out, n_invalid, *, M, C, L, H, W, member_stride, lead_stride, channel_stride,
+                     truth_slot_stride, truth_channel_stride, mean=None, std=None, target_std=1.0, L_total, l_off=0):
+    """out [3][C][L_total][W / 2 + 1] = spec_members, spec_mean, spec_truth; n_invalid (int32) [C][L_total]: columns l_off .. l_off + L - 1
+    of L lead times in one launch (ladcast_hip.h: ldc_rollout_spectrum); truth_slot: device int32 [L]; row_weight: device fp32 [H], >= 0"""
+    _dev(forecast, truth, truth_slot, row_weight, out, n_invalid, mean, std)
+    nbytes = int(lib.ldc_rollout_spectrum_workspace_bytes(M, C, L, H, W))
+    ws = _workspace("rollout_spectrum", forecast.device, max(nbytes, 4), grow=True)
+    _check(lib.ldc_rollout_spectrum(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
+                                    truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(row_weight), M, C, L, H, W, _p(out),
+                                    _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_spectrum")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):
