@@ -631,6 +631,42 @@ int ldc_rollout_spectrum(const float* forecast, long long member_stride, long lo
                          long long truth_channel_stride, const int* truth_slot, const float* row_weight, int M, int C, int L, int H,
                          int W, float* out, int* n_invalid, int L_total, int l_off, void* workspace, long long workspace_bytes,
                          void* stream);
+/* Ensemble products for every lead time of a decode batch in one launch (additive under ABI 5; products.hip):
+ * per grid point the ensemble mean, spread, range, quantiles and probabilities of exceeding a threshold.  Not in the reference.  There
+ * is no truth.  Addressing of forecast, inverse normalisation (mean == NULL: physical units; mean / std_ indexed by the ORIGINAL
+ * channel) and output columns exactly as ldc_rollout_scores; pointwise, so no workspace.
+ * channels: optional device int32 [Cs], indices into the C channels in any order; NULL: all channels (Cs must equal C).  The outputs
+ *   hold Cs channels in list order.  The indices are the caller's responsibility (the call cannot read device memory).
+ * Per point, the M members x_i in member order after the inverse normalisation:
+ *   stats [4][Cs][L_total][H][W] = mean, std, min, max: mean = (sequential fp32 sum) / M; std = sqrt(sum_i (x_i - mean)^2 / (M - 1)),
+ *     two-pass (M == 1: NaN), the variance of ldc_rollout_reliability
+ *   quant [Q][Cs][L_total][H][W], Q = desc->n_quant <= LDC_PRODUCTS_MAX_QUANTILES: quantile k is given as (q_lo[k], q_t[k]), which the
+ *     host derives from q in [0, 1] in float64: pos = q (M - 1), lo = min(floor(pos), M - 1), t = float(pos - lo).  With the sorted
+ *     members x_(0) <= ... <= x_(M-1): x_(lo) untouched when t == 0, else a + (b - a) * t, a = x_(lo), b = x_(min(lo + 1, M - 1)), three
+ *     fp32 operations without contraction (numpy's method="linear").  0 <= q_lo <= M - 1 and 0 <= q_t <= 1 are checked.
+ *   exceed [P][Cs][L_total][H][W], P = desc->n_thr <= LDC_PRODUCTS_MAX_THRESHOLDS: thr [P][Cs] fp32 on the device, in physical units;
+ *     thr_dir[k] = +1: #{x_i > thr} / M, -1: #{x_i < thr} / M.  A NaN threshold makes that (k, channel) plane NaN.
+ *   A point with a NaN member is NaN in every output; +-inf are ordinary ordered values (IEEE arithmetic).
+ *   Each output pointer is optional: NULL = not computed, not written.  Columns l_off .. l_off + L - 1 are written, the others left alone.
+ * With quantiles the members are sorted in registers: M <= 64.  Without (Q == 0 or quant == NULL): 1 <= M <= 1024.
+ * LDC_ERR_ARG: a null forecast or desc, a non-positive size (M <= 0 among them), l_off + L > L_total, channels == NULL with Cs != C,
+ * more quantiles or thresholds than the caps, a (q_lo, q_t) out of range, a direction that is not +-1, thr == NULL with thresholds, or
+ * no output at all; LDC_ERR_UNSUPPORTED: M > 1024, M > 64 with quantiles, Cs > 65535, L > 65535 or H * W > 2^24.  Nothing is launched
+ * on an error. */
+#define LDC_PRODUCTS_MAX_QUANTILES 16
+#define LDC_PRODUCTS_MAX_THRESHOLDS 8
+typedef struct ldc_products_desc {
+  int n_quant; /* Q */
+  int n_thr;   /* P */
+  int q_lo[LDC_PRODUCTS_MAX_QUANTILES];
+  float q_t[LDC_PRODUCTS_MAX_QUANTILES];
+  int thr_dir[LDC_PRODUCTS_MAX_THRESHOLDS];
+} ldc_products_desc;
+int ldc_sizeof_products_desc(void);
+int ldc_rollout_products(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride,
+                         const float* mean, const float* std_, float target_std, const int* channels, int M, int C, int Cs, int L, int H,
+                         int W, const ldc_products_desc* desc, const float* thr, float* stats, float* quant, float* exceed, int L_total,
+                         int l_off, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

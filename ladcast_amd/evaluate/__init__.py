@@ -1,12 +1,14 @@
-from .utils import (VALIDATION_SCORE_NAMES, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
-                    get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_reliability, rollout_scores, rollout_spectrum, validation_scores)
+from .utils import (VALIDATION_SCORE_NAMES, empty_products, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
+                    get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_products, rollout_reliability, rollout_scores, rollout_spectrum,
+                    validation_scores)
 
 _DRIVER_NAMES = ("climatology_slots", "score_latent_rollout", "truth_frame_slots")  # evaluate_ens_gpu's, resolved at first use: the
 _VALIDATE_NAMES = ("NpyLatentStore", "log_validation", "validate_initial_time")  # validate_AR's, likewise
 _DENOISE_NAMES = ("denoising_loss", "evaluate_denoising_loss", "push_forward_plan")  # denoise_loss's, likewise
+_PRODUCTS_NAMES = ("products_of_latent_rollout",)  # products', likewise
 __all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
            "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores", "rollout_spectrum",  # also runs
-           "validation_scores", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES]  # as `python -m`
+           "validation_scores", "empty_products", "rollout_products", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES]  # as `python -m`
 
 
 def __getattr__(name):
@@ -22,4 +24,8 @@ def __getattr__(name):
         from . import denoise_loss
 
         return getattr(denoise_loss, name)
+    if name in _PRODUCTS_NAMES:
+        from . import products
+
+        return getattr(products, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -396,3 +396,117 @@ def rollout_spectrum(forecast: torch.Tensor, truth: torch.Tensor, row_weight: to
                          channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
                          target_std=target_std, L_total=bufs[0].shape[2], l_off=l_off)
     return SpectrumDict(*bufs)
+
+
+PRODUCT_STAT_NAMES = ("mean", "std", "min", "max")  # the planes of ldc_rollout_products' `stats`, in order
+MAX_PRODUCT_QUANTILES, MAX_PRODUCT_THRESHOLDS = hip.PRODUCTS_MAX_QUANTILES, hip.PRODUCTS_MAX_THRESHOLDS
+MAX_PRODUCT_MEMBERS, MAX_PRODUCT_SORT_MEMBERS = hip.PRODUCTS_MAX_MEMBERS, hip.PRODUCTS_MAX_SORT_MEMBERS
+
+
+class ProductsDict(dict):
+    """{mean, std, min, max: (Cs, L_total, H, W); quantiles: (Q, Cs, L_total, H, W); exceed: (P, Cs, L_total, H, W)}, fp32 views over the
+    three device buffers `ldc_rollout_products` fills; a buffer that is None (output not asked for) leaves its keys out"""
+
+    def __init__(self, stats, quant, exceed):
+        super().__init__()
+        if stats is not None:
+            self.update({k: stats[i] for i, k in enumerate(PRODUCT_STAT_NAMES)})
+        if quant is not None:
+            self["quantiles"] = quant
+        if exceed is not None:
+            self["exceed"] = exceed
+        self._buffers = (stats, quant, exceed)
+
+
+def empty_products(Cs: int, L_total: int, H: int, W: int, device, *, n_quantiles: int = 0, n_thresholds: int = 0, stats: bool = True) -> ProductsDict:
+    """the result of `rollout_products` before any column is written: NaN everywhere"""
+    new = lambda n: torch.full((n, Cs, L_total, H, W), float("nan"), device=device, dtype=torch.float32)  # noqa: E731
+    return ProductsDict(new(len(PRODUCT_STAT_NAMES)) if stats else None, new(n_quantiles) if n_quantiles else None,
+                        new(n_thresholds) if n_thresholds else None)
+
+
+@torch.no_grad()
+def rollout_products(forecast: torch.Tensor, *, quantiles=(), thresholds=None, threshold_dirs=None, channels=None, stats: bool = True,
+                     lead_dim: int = 2, mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, target_std: float = 1.0,
+                     out: Optional[Dict[str, torch.Tensor]] = None, l_off: int = 0) -> Dict[str, torch.Tensor]:
+    """Ensemble products of every lead time in one launch (`ldc_rollout_products`; not in the reference): per grid point, with the M
+    members x_i in member order, `mean` = sum_i x_i / M, `std` = sqrt(sum_i (x_i - mean)^2 / (M - 1)) (NaN for one member), `min`, `max`,
+    `quantiles[k]` = numpy's `quantile(x, q_k, method="linear")` and `exceed[p]` = the fraction of members above (direction +1) or below
+    (-1) `thresholds[p, channel]`.  A point with a NaN member is NaN in every product, a NaN threshold makes its plane NaN; +-inf are
+    ordinary ordered values.  1 <= M <= 1024 without quantiles, M <= 64 with (the members are sorted in registers).
+
+    `quantiles`: up to 16 values in [0, 1].  `thresholds`: (P, Cs) fp32, P <= 8, in physical units (after the inverse normalisation), one
+    row per threshold and one column per selected channel; `threshold_dirs`: P values +1 / -1 (default: all +1).  `channels`: indices into
+    the forecast's C channels in any order (default: all); the outputs hold these Cs channels in this order and `mean` / `std` stay
+    indexed by the original channel.  `stats=False` leaves mean / std / min / max out.  forecast, `lead_dim`, `mean` / `std` /
+    `target_std`: as `rollout_scores`.  Returns a `ProductsDict` of device views with L_total = l_off + L columns (unwritten columns NaN),
+    or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_products`) returned."""
+    if forecast.dim() != 5 or lead_dim not in (0, 2):
+        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
+    if forecast.dtype != torch.float32:
+        raise NotImplementedError("fp32 only")
+    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
+    M, C, L, H, W = f.shape
+    qs = [float(q) for q in (quantiles.tolist() if isinstance(quantiles, torch.Tensor) else quantiles)]
+    if not 1 <= M <= MAX_PRODUCT_MEMBERS:
+        raise ValueError(f"{M} members: ldc_rollout_products serves 1 .. {MAX_PRODUCT_MEMBERS}")
+    if qs and M > MAX_PRODUCT_SORT_MEMBERS:
+        raise ValueError(f"{M} members: quantiles need the members sorted in registers, at most {MAX_PRODUCT_SORT_MEMBERS}")
+    if channels is None:
+        chan = None
+        Cs = C
+    else:
+        chan = [int(c) for c in (channels.tolist() if isinstance(channels, torch.Tensor) else channels)]
+        if not chan or any(not 0 <= c < C for c in chan):
+            raise ValueError(f"channels {chan} must be a non-empty list of indices into the forecast's {C} channels")
+        Cs = len(chan)
+    P = 0
+    if thresholds is not None:
+        thresholds = torch.as_tensor(thresholds, dtype=torch.float32)
+        if thresholds.dim() != 2 or thresholds.shape[1] != Cs or thresholds.shape[0] < 1:
+            raise ValueError(f"thresholds must be (P, Cs) = (P, {Cs}), one row per threshold, got {tuple(thresholds.shape)}")
+        P = thresholds.shape[0]
+    dirs = [1] * P if threshold_dirs is None else [int(d) for d in (threshold_dirs.tolist() if isinstance(threshold_dirs, torch.Tensor) else threshold_dirs)]
+    if len(dirs) != P:
+        raise ValueError(f"{len(dirs)} threshold directions for {P} thresholds")
+    desc = hip.products_desc(qs, M, dirs)  # ValueError: too many, q outside [0, 1] or NaN, a direction that is not +-1
+    Q = len(qs)
+    if not (stats or Q or P):
+        raise ValueError("nothing to compute: no stats, no quantiles, no thresholds")
+    if l_off < 0:
+        raise ValueError("l_off must not be negative")
+    dev = f.device
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
+        if mean.numel() != C or std.numel() != C:
+            raise ValueError(f"mean / std must hold one value per channel ({C})")
+    if out is None:
+        hip._dev(forecast)
+        bufs = empty_products(Cs, l_off + L, H, W, dev, n_quantiles=Q, n_thresholds=P, stats=stats)._buffers
+    else:
+        bufs = getattr(out, "_buffers", None)
+        ok = bufs is not None and len(bufs) == 3
+        if ok:
+            want = (len(PRODUCT_STAT_NAMES) if stats else 0, Q, P)
+            Lt = next((b.shape[2] for b in bufs if b is not None and b.dim() == 5), None)
+            ok = Lt is not None and l_off + L <= Lt
+            for b, n in zip(bufs, want):
+                if n == 0:
+                    continue  # not asked for in this call: left alone
+                ok = ok and b is not None and tuple(b.shape) == (n, Cs, Lt, H, W) and b.dtype == torch.float32 and b.is_contiguous() and b.device == dev
+        if not ok:
+            raise ValueError("out must be the dict an earlier rollout_products call (or empty_products) returned for the same channels, "
+                             "quantiles, thresholds and grid, with room for columns l_off .. l_off + L - 1")
+    hip._dev(forecast)
+    if f.stride(-1) != 1 or f.stride(-2) != W:
+        f = f.contiguous()
+    st, qu, ex = (b if n else None for b, n in zip(bufs, (stats, Q, P)))
+    L_total = next(b.shape[2] for b in (st, qu, ex) if b is not None)
+    chan_d = None if chan is None else hip.upload_nonblocking(torch.tensor(chan, dtype=torch.int32), dev)
+    thr_d = None if P == 0 else (thresholds if thresholds.is_cuda else hip.upload_nonblocking(thresholds.contiguous(), dev)).contiguous()
+    hip.rollout_products(f, desc, M=M, C=C, Cs=Cs, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2), channel_stride=f.stride(1),
+                         channels=chan_d, thr=thr_d, stats=st, quant=qu, exceed=ex, mean=mean, std=std, target_std=target_std, L_total=L_total,
+                         l_off=l_off)
+    return ProductsDict(*bufs)

@@ -53,6 +53,14 @@ class LinearSmallProblem(Structure):  # ldc_linear_small_problem
                 ("rows", c_int), ("N", c_int), ("K", c_int), ("act_in", c_int), ("act_out", c_int), ("reserved", c_int)]
 
 
+PRODUCTS_MAX_QUANTILES, PRODUCTS_MAX_THRESHOLDS, PRODUCTS_MAX_MEMBERS, PRODUCTS_MAX_SORT_MEMBERS = 16, 8, 1024, 64  # LDC_PRODUCTS_MAX_*
+
+
+class ProductsDesc(Structure):  # ldc_products_desc
+    _fields_ = [("n_quant", c_int), ("n_thr", c_int), ("q_lo", c_int * PRODUCTS_MAX_QUANTILES), ("q_t", c_float * PRODUCTS_MAX_QUANTILES),
+                ("thr_dir", c_int * PRODUCTS_MAX_THRESHOLDS)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
@@ -112,6 +120,8 @@ def _load():
         "ldc_rollout_reliability": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, L, P]),
         "ldc_rollout_spectrum_workspace_bytes": (L, [I, I, I, I, I]),
         "ldc_rollout_spectrum": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, P, P, I, I, P, L, P]),
+        "ldc_sizeof_products_desc": (I, []),
+        "ldc_rollout_products": (I, [P, L, L, L, P, P, F, P, I, I, I, I, I, I, POINTER(ProductsDesc), P, P, P, P, I, I, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
         "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
         "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
@@ -166,6 +176,8 @@ def _load():
         raise RuntimeError("ldc_gemm_desc / ldc_gemm_problem layout mismatch between header and binding")
     if lib.ldc_sizeof_qkv_epilogue() != ctypes.sizeof(QkvEpilogue):
         raise RuntimeError("ldc_qkv_epilogue layout mismatch between header and binding")
+    if lib.ldc_sizeof_products_desc() != ctypes.sizeof(ProductsDesc):
+        raise RuntimeError("ldc_products_desc layout mismatch between header and binding")
     return lib, sig
 
 
@@ -427,6 +439,42 @@ def rollout_spectrum(forecast, truth, truth_slot, row_weight, out, n_invalid, *,
     _check(lib.ldc_rollout_spectrum(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
                                     truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(row_weight), M, C, L, H, W, _p(out),
                                     _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_spectrum")
+
+
+def products_desc(quantiles, M, threshold_dirs=()):
+    """ldc_products_desc for quantiles q in [0, 1] of M members and one direction (+1: above, -1: below) per threshold.  In float64:
+    pos = q (M - 1), lo = min(floor(pos), M - 1), t = float32(pos - lo) - numpy's method="linear".  Host arithmetic only."""
+    import math
+
+    qs, dirs = [float(q) for q in quantiles], [int(d) for d in threshold_dirs]
+    if len(qs) > PRODUCTS_MAX_QUANTILES or len(dirs) > PRODUCTS_MAX_THRESHOLDS:
+        raise ValueError(f"at most {PRODUCTS_MAX_QUANTILES} quantiles and {PRODUCTS_MAX_THRESHOLDS} thresholds per call")
+    if any(not 0.0 <= q <= 1.0 for q in qs):  # NaN fails the comparison too
+        raise ValueError(f"quantiles must lie in [0, 1], got {qs}")
+    if any(d not in (1, -1) for d in dirs):
+        raise ValueError(f"a threshold direction is +1 (above) or -1 (below), got {dirs}")
+    if M < 1:
+        raise ValueError("at least one member")
+    d = ProductsDesc()
+    d.n_quant, d.n_thr = len(qs), len(dirs)
+    for k, q in enumerate(qs):
+        pos = q * (M - 1)
+        lo = min(int(math.floor(pos)), M - 1)
+        d.q_lo[k], d.q_t[k] = lo, pos - lo  # the field rounds to fp32
+    for k, v in enumerate(dirs):
+        d.thr_dir[k] = v
+    return d
+
+
+def rollout_products(forecast, desc, *, M, C, L, H, W, member_stride, lead_stride, channel_stride, channels=None, Cs=None, thr=None, stats=None,
+                     quant=None, exceed=None, mean=None, std=None, target_std=1.0, L_total, l_off=0):
+    """stats [4][Cs][L_total][H][W] = mean, std, min, max; quant [Q][Cs][L_total][H][W]; exceed [P][Cs][L_total][H][W]: columns
+    l_off .. l_off + L - 1 of L lead times in one launch, each output optional (ladcast_hip.h: ldc_rollout_products); desc:
+    `products_desc`; channels: device int32 [Cs] or None (all); thr: device fp32 [P][Cs]"""
+    _dev(forecast, channels, thr, stats, quant, exceed, mean, std)
+    _check(lib.ldc_rollout_products(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(channels),
+                                    M, C, C if Cs is None else Cs, L, H, W, ctypes.byref(desc), _p(thr), _p(stats), _p(quant), _p(exceed),
+                                    L_total, l_off, _stream()), "ldc_rollout_products")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):
