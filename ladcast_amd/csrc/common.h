@@ -15,9 +15,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
   do {                   \
     if ((p) == nullptr) return LDC_ERR_ARG; \
   } while (0)
+static inline bool ldc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 #define LDC_CHECK_ALIGN16(p) \
   do {                       \
-    if ((reinterpret_cast<uintptr_t>(p) & 15u) != 0) return LDC_ERR_ALIGN; \
+    if (!ldc_aligned16(p)) return LDC_ERR_ALIGN; \
   } while (0)
 
 static inline int ldc_launch_status() {
@@ -128,6 +129,16 @@ int ldc_conv_halo_dispatch(const float* X, const void* Wp, const float* bias, co
 
 // wave64 butterfly reductions
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

@@ -39,12 +39,6 @@ __global__ void edm_denoise_kernel(const float* __restrict__ noisy, const float*
   denoised[row * den_row + j] = a + g;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One wave per (b, c, t) plane.  Lane l takes elements l, l + 64, ... of the plane in that order into its own fp64 sum; the 64 sums go
 // through the xor butterfly (a fixed tree: both operands of every add are the same values in every lane, so all lanes end with the same
 // bits); one fp64 division by the plane size, one rounding to fp32.  No atomics, nothing that depends on which wave runs when.
@@ -74,7 +68,7 @@ __global__ void __launch_bounds__(64 * LOSS_WAVES)
     const float term = w * q;
     acc += static_cast<double>(term);
   }
-  acc = wave_sum_f64(acc);
+  acc = wave_sum(acc);
   if (lane == 0) table[pl] = static_cast<float>(acc / static_cast<double>(plane));
 }
 

@@ -49,12 +49,6 @@ struct MomArgs {
   int B, H, W, rows, wseg, ncc, nchunk;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int V>  // V = 4: 16-byte loads (W % 4 == 0, aligned base and strides), V = 1: scalar
 __global__ __launch_bounds__(TPB) void field_moments_kernel(MomArgs a) {
   __shared__ double red1[TPB / 64][2];
@@ -100,8 +94,8 @@ __global__ __launch_bounds__(TPB) void field_moments_kernel(MomArgs a) {
     cnt += ok ? 1.0 : 0.0;
     sum += ok ? static_cast<double>(v[k]) : 0.0;
   }
-  cnt = wave_sum_f64(cnt);
-  sum = wave_sum_f64(sum);
+  cnt = wave_sum(cnt);
+  sum = wave_sum(sum);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     red1[wave][0] = cnt;
@@ -121,8 +115,8 @@ __global__ __launch_bounds__(TPB) void field_moments_kernel(MomArgs a) {
     s += d;
     q = fma(d, d, q);
   }
-  s = wave_sum_f64(s);
-  q = wave_sum_f64(q);
+  s = wave_sum(s);
+  q = wave_sum(q);
   if ((threadIdx.x & 63) == 0) {
     red2[wave][0] = s;
     red2[wave][1] = q;
@@ -155,8 +149,8 @@ __global__ __launch_bounds__(64) void field_moments_finish_kernel(const double* 
     n += ni;
     t0 = fma(ni, src[k * NP + 1], t0);
   }
-  n = wave_sum_f64(n);
-  t0 = wave_sum_f64(t0);
+  n = wave_sum(n);
+  t0 = wave_sum(t0);
   const double K = n > 0.0 ? t0 / n : 0.0;
   double t = 0.0, u = 0.0;
   for (long long k = threadIdx.x; k < nrec; k += 64) {
@@ -164,8 +158,8 @@ __global__ __launch_bounds__(64) void field_moments_finish_kernel(const double* 
     t += nd;
     u += fma(nd, d, src[k * NP + 2]);
   }
-  t = wave_sum_f64(t);
-  u = wave_sum_f64(u);
+  t = wave_sum(t);
+  u = wave_sum(u);
   if (threadIdx.x != 0) return;
   double mean = NAN, m2 = NAN;  // no valid value: numpy's nanmean
   if (n > 0.0) {
@@ -188,8 +182,6 @@ __global__ __launch_bounds__(64) void field_moments_finish_kernel(const double* 
   st[1] = mean;
   st[2] = m2;
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 constexpr long long MAX_RECORDS = (1ll << 24) - 1;  // grid.x * TPB threads of the first launch stay below 2^32
 
@@ -223,7 +215,7 @@ extern "C" int ldc_field_moments(const float* x, long long batch_stride, long lo
   if ((reinterpret_cast<uintptr_t>(state) & 7u) != 0 || (reinterpret_cast<uintptr_t>(x) & 3u) != 0) return LDC_ERR_ALIGN;
   const Geometry g = geometry(H, W);
   MomArgs a{x, batch_stride, channel_stride, row_stride, static_cast<double*>(workspace), B, H, W, g.rows, g.wseg, g.ncc, static_cast<int>(g.nchunk)};
-  const bool vec = W % 4 == 0 && aligned16(x) && batch_stride % 4 == 0 && channel_stride % 4 == 0 && row_stride % 4 == 0;
+  const bool vec = W % 4 == 0 && ldc_aligned16(x) && batch_stride % 4 == 0 && channel_stride % 4 == 0 && row_stride % 4 == 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (vec) hipLaunchKernelGGL(field_moments_kernel<4>, dim3(static_cast<unsigned>(nrec)), dim3(TPB), 0, s, a);
   else hipLaunchKernelGGL(field_moments_kernel<1>, dim3(static_cast<unsigned>(nrec)), dim3(TPB), 0, s, a);

@@ -1,7 +1,8 @@
 // Ensemble products of a decoded forecast: per grid point the ensemble mean, spread, range, quantile maps and
 // probabilities of exceeding a threshold - what an ensemble forecast is consumed as, for a forecast that has no truth yet.  Not in the
 // reference.  The forecast is addressed as ldc_rollout_scores (scoring.hip) addresses it: member / lead / channel strides, a contiguous
-// (H, W) plane, the optional fused inverse normalisation; grid (point blocks, selected channel, lead time), output columns at l_off.
+// (H, W) plane, the optional fused inverse normalisation (inv_norm, ensemble_common.h); grid (point blocks, selected channel, lead time),
+// output columns at l_off.
 // Pointwise: one thread per grid point, consecutive threads along W (coalesced loads and stores), no workspace, no reduction.
 // Per point, M members x_i in member order (after the inverse normalisation):
 //   mean = (x_0 + ... + x_{M-1}) / M                       sequential fp32 sum
@@ -11,13 +12,13 @@
 //     (lo, t) come from the host (float64 arithmetic on q (M - 1)); three fp32 operations, the file is built with -ffp-contract=off
 //   exceed (thr, dir): #{x_i > thr} / M (dir +1) or #{x_i < thr} / M (dir -1); a NaN threshold gives NaN
 // A point with a NaN member is NaN in every output; +-inf are ordinary ordered values.
-// Two arms.  With quantiles the members live in registers and are sorted by the pruned odd-even merge network of scoring.hip (M <= 64,
+// Two arms.  With quantiles the members live in registers and are sorted by the pruned odd-even merge network of ensemble_common.h (M <= 64,
 // the same (NP, NUSE) ladder); a and b are picked by an unrolled compare-and-select over the registers, because a runtime index would
 // send the array to scratch.  Without quantiles nothing is sorted: the streaming arm serves 1 <= M <= 1024 and reads the members a
 // second time for the squared deviations.
 #include <math.h>
 
-#include "common.h"
+#include "ensemble_common.h"
 
 namespace {
 
@@ -42,43 +43,6 @@ struct ProdArgs {
   int Q, P;  // 0 when the output is not asked for
   ldc_products_desc d;
 };
-
-// Batcher's odd-even merge sort for NP = 2^k registers, fully unrolled; comparators that touch an index >= NUSE (+inf padding) are
-// pruned at compile time (scoring.hip)
-template <int NP, int NUSE>
-__device__ __forceinline__ void sort_network(float (&x)[NP]) {
-#pragma unroll
-  for (int p = 1; p < NP; p <<= 1) {
-#pragma unroll
-    for (int k = p; k >= 1; k >>= 1) {
-#pragma unroll
-      for (int j = k % p; j <= NP - 1 - k; j += 2 * k) {
-#pragma unroll
-        for (int i = 0; i < k; ++i) {
-          const int lo_i = i + j, hi_i = i + j + k;
-          if (hi_i < NUSE && (lo_i / (2 * p)) == (hi_i / (2 * p))) {
-            const float a = x[lo_i], b = x[hi_i];
-            x[lo_i] = fminf(a, b);
-            x[hi_i] = fmaxf(a, b);
-          }
-        }
-      }
-    }
-  }
-}
-
-// the inverse normalisation of scoring.hip / ldc_chan_affine(inverse=1): (v / target_std) * sd + mn, each operation rounded on its own
-// (this file is built without contraction); x / 1 == x: the division is skipped for the default target_std
-struct InvNorm {
-  float target_std, sd, mn;
-  bool unit;
-};
-
-__device__ __forceinline__ float inv_norm(float v, const InvNorm& n) {
-  const float q = n.unit ? v : v / n.target_std;
-  const float m = q * n.sd;
-  return m + n.mn;
-}
 
 // what the first pass over the members gathers, in member order
 struct Pass1 {
@@ -116,7 +80,7 @@ __global__ __launch_bounds__(TPB) void products_kernel(ProdArgs a) {
   const int M = a.M, P = a.P;
   const float* f = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs + p;
   InvNorm nrm{};
-  if constexpr (INV) nrm = InvNorm{a.target_std, a.sd[c], a.mean[c], a.target_std == 1.0f};
+  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
   float thr[MAX_P];
   unsigned gt_mask = 0u;
 #pragma unroll
@@ -204,16 +168,11 @@ __global__ __launch_bounds__(TPB) void products_kernel(ProdArgs a) {
 
 template <bool INV>
 void launch_products(const ProdArgs& a, dim3 grid, hipStream_t s) {
-  const int M = a.M;
   if (a.Q == 0) hipLaunchKernelGGL((products_kernel<0, 0, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 8) hipLaunchKernelGGL((products_kernel<8, 8, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 16) hipLaunchKernelGGL((products_kernel<16, 16, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 24) hipLaunchKernelGGL((products_kernel<32, 24, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 32) hipLaunchKernelGGL((products_kernel<32, 32, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 40) hipLaunchKernelGGL((products_kernel<64, 40, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 48) hipLaunchKernelGGL((products_kernel<64, 48, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 56) hipLaunchKernelGGL((products_kernel<64, 56, INV>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((products_kernel<64, 64, INV>), grid, dim3(TPB), 0, s, a);
+  else
+    ldc_dispatch_sort_arm(a.M, [&](auto np, auto nuse) {
+      hipLaunchKernelGGL((products_kernel<decltype(np)::value, decltype(nuse)::value, INV>), grid, dim3(TPB), 0, s, a);
+    });
 }
 
 }  // namespace
@@ -226,10 +185,8 @@ extern "C" int ldc_rollout_products(const float* forecast, long long member_stri
                                     int L_total, int l_off, void* stream) {
   LDC_CHECK_PTR(forecast);
   LDC_CHECK_PTR(desc);
-  if (mean != nullptr) LDC_CHECK_PTR(std_);
-  if (M <= 0 || C <= 0 || Cs <= 0 || L <= 0 || H <= 0 || W <= 0 || L_total <= 0 || l_off < 0) return LDC_ERR_ARG;
-  if (static_cast<long long>(l_off) + L > L_total) return LDC_ERR_ARG;
-  if (channels == nullptr && Cs != C) return LDC_ERR_ARG;
+  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
+  if (Cs <= 0 || (channels == nullptr && Cs != C)) return LDC_ERR_ARG;
   if (desc->n_quant < 0 || desc->n_quant > MAX_Q || desc->n_thr < 0 || desc->n_thr > MAX_P) return LDC_ERR_ARG;
   const int Q = quant != nullptr ? desc->n_quant : 0;
   const int P = exceed != nullptr ? desc->n_thr : 0;

@@ -162,8 +162,6 @@ __global__ __launch_bounds__(64) void recon_scores_finish_kernel(const float* __
   if (threadIdx.x == 0) lw_mse[c] = lw / npoints;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int ldc_recon_preprocess(const float* x, long long batch_stride, long long channel_stride, long long row_stride, int B,
@@ -178,7 +176,7 @@ extern "C" int ldc_recon_preprocess(const float* x, long long batch_stride, long
   if (B > 65535 || C > 65535) return LDC_ERR_UNSUPPORTED;
   PreArgs a{x, batch_stride, channel_stride, row_stride, mean, std_, out, nan_mask, C, H, W, sst_channel < 0 ? -1 : sst_channel};
   const long long HW = static_cast<long long>(H) * W;
-  const bool vec = W % 4 == 0 && aligned16(x) && aligned16(out) && batch_stride % 4 == 0 && channel_stride % 4 == 0 && row_stride % 4 == 0;
+  const bool vec = W % 4 == 0 && ldc_aligned16(x) && ldc_aligned16(out) && batch_stride % 4 == 0 && channel_stride % 4 == 0 && row_stride % 4 == 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (vec) hipLaunchKernelGGL(recon_preprocess_kernel<4>, dim3(ldc_cdiv(HW / 4, TPB), C, B), dim3(TPB), 0, s, a);
   else hipLaunchKernelGGL(recon_preprocess_kernel<1>, dim3(ldc_cdiv(HW, TPB), C, B), dim3(TPB), 0, s, a);
@@ -224,7 +222,7 @@ extern "C" int ldc_recon_scores(const float* pred, const float* target, const fl
   a.rows = chunk_rows(W);
   a.nchunk = ldc_cdiv(H, a.rows);
   // 16-byte loads: every plane and every chunk of whole rows starts on a 16-byte boundary (the mask: on a 4-byte one)
-  const bool vec = W % 4 == 0 && aligned16(pred) && aligned16(target) && (S == 0 || (aligned16(static_) && static_batch_stride % 4 == 0)) &&
+  const bool vec = W % 4 == 0 && ldc_aligned16(pred) && ldc_aligned16(target) && (S == 0 || (ldc_aligned16(static_) && static_batch_stride % 4 == 0)) &&
                    (a.mask == nullptr || (reinterpret_cast<uintptr_t>(a.mask) & 3u) == 0);
   hipStream_t s = static_cast<hipStream_t>(stream);
   dim3 grid(a.nchunk, B * Cp);

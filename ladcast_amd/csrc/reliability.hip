@@ -1,7 +1,8 @@
 // Ensemble reliability of a decoded forecast: spread-skill ratio and rank histogram per (channel, lead time).
 // Not in the reference (ladcast/evaluate/utils.py stops at CRPS and ACC); the pair WeatherBench2 reports beside CRPS.
 // Addressing is that of ldc_rollout_scores (scoring.hip): forecast by member / lead / channel strides, optional fused inverse
-// normalisation, truth as a table of planes with a slot per lead time, lat_weight[H], grid (point blocks, C, L), output columns at l_off.
+// normalisation (inv_norm, ensemble_common.h), truth as a table of planes with a slot per lead time, lat_weight[H], grid (point blocks,
+// C, L), output columns at l_off.
 // Per grid point, M members x_i in member order, truth t, weight w:
 //   mean = (x_0 + ... + x_{M-1}) / M          (the sum of score_point, scoring.hip: ens_mse holds ldc_rollout_scores' bits for M <= 64)
 //   se   = (mean - t)^2
@@ -19,7 +20,7 @@
 //     bin b adds the records' entries in record order.
 #include <math.h>
 
-#include "common.h"
+#include "ensemble_common.h"
 
 namespace {
 
@@ -46,25 +47,6 @@ struct RelArgs {
   int ntile, tpw, nrec;
 };
 
-// the inverse normalisation of scoring.hip / ldc_chan_affine(inverse=1): (v / target_std) * sd + mn, each operation rounded on its own
-// (this file is built without contraction); x / 1 == x: the division is skipped for the default target_std
-struct InvNorm {
-  float target_std, sd, mn;
-  bool unit;
-};
-
-__device__ __forceinline__ float inv_norm(float v, const InvNorm& n) {
-  const float q = n.unit ? v : v / n.target_std;
-  const float m = q * n.sd;
-  return m + n.mn;
-}
-
-__device__ __forceinline__ int wave_total_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // NMAX > 0: M <= NMAX members in registers; NMAX == 0: any M, the members are read again for the variance
 template <int NMAX, bool INV>
 __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
@@ -81,7 +63,7 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
   const float* fbase = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs;
   const float* tbase = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs;
   InvNorm nrm{};
-  if constexpr (INV) nrm = InvNorm{a.target_std, a.sd[c], a.mean[c], a.target_std == 1.0f};
+  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
   const float Mf = static_cast<float>(M);
   float acc_se = 0.f, acc_var = 0.f;
   int n_se = 0, n_var = 0, n_in = 0, n_inv = 0;
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
   }
   const int wave = tid >> 6;
   const float r_se = wave_sum(acc_se), r_var = wave_sum(acc_var);
-  const int i_se = wave_total_i(n_se), i_var = wave_total_i(n_var), i_in = wave_total_i(n_in), i_inv = wave_total_i(n_inv);
+  const int i_se = wave_sum(n_se), i_var = wave_sum(n_var), i_in = wave_sum(n_in), i_inv = wave_sum(n_inv);
   if ((tid & 63) == 0) {
     red_f[wave][0] = r_se;
     red_f[wave][1] = r_var;
@@ -245,10 +227,10 @@ __global__ __launch_bounds__(TPB) void reliability_finish_kernel(const unsigned*
   }
   s_se = wave_sum(s_se);
   s_var = wave_sum(s_var);
-  k_se = wave_total_i(k_se);
-  k_var = wave_total_i(k_var);
-  k_in = wave_total_i(k_in);
-  k_inv = wave_total_i(k_inv);
+  k_se = wave_sum(k_se);
+  k_var = wave_sum(k_var);
+  k_in = wave_sum(k_in);
+  k_inv = wave_sum(k_inv);
   if (threadIdx.x != 0) return;
   const float nanv = __builtin_nanf("");
   const bool nanmean = c == nan_channel;
@@ -300,9 +282,7 @@ extern "C" int ldc_rollout_reliability(const float* forecast, long long member_s
   LDC_CHECK_PTR(hist_weight);
   LDC_CHECK_PTR(n_invalid);
   LDC_CHECK_PTR(workspace);
-  if (mean != nullptr) LDC_CHECK_PTR(std_);
-  if (M <= 0 || C <= 0 || L <= 0 || H <= 0 || W <= 0 || L_total <= 0 || l_off < 0) return LDC_ERR_ARG;
-  if (static_cast<long long>(l_off) + L > L_total) return LDC_ERR_ARG;
+  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (M > MAX_M || C > 65535 || L > 65535 || static_cast<long long>(H) * W > (1ll << 24)) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_reliability_workspace_bytes(M, C, L, H, W)) return LDC_ERR_ARG;
   RelArgs a{};

@@ -21,7 +21,7 @@
 // hook (train_AR.py:281-312): ens_mse = mean_hw[(mean_i x_i - t)^2 w], single_mse = mean_{i,hw}[(x_i - t)^2 w], crps; plain mean everywhere.
 #include <math.h>
 
-#include "common.h"
+#include "ensemble_common.h"
 
 namespace {
 
@@ -43,53 +43,6 @@ struct ScoreArgs {
   float* part;        // [C][nblk][NQ + 1]
   int nblk;
 };
-
-// Batcher's odd-even merge sort for NP = 2^k registers, fully unrolled (compile-time register indices).  Every
-// comparator is ascending (min to the lower index), so comparators that touch an index >= NUSE -- registers that hold
-// the +inf padding behind the members -- are no-ops and are pruned at compile time.
-template <int NP, int NUSE>
-__device__ __forceinline__ void sort_network(float (&x)[NP]) {
-#pragma unroll
-  for (int p = 1; p < NP; p <<= 1) {
-#pragma unroll
-    for (int k = p; k >= 1; k >>= 1) {
-#pragma unroll
-      for (int j = k % p; j <= NP - 1 - k; j += 2 * k) {
-#pragma unroll
-        for (int i = 0; i < k; ++i) {
-          const int lo_i = i + j, hi_i = i + j + k;
-          if (hi_i < NUSE && (lo_i / (2 * p)) == (hi_i / (2 * p))) {
-            const float a = x[lo_i], b = x[hi_i];
-            x[lo_i] = fminf(a, b);
-            x[hi_i] = fmaxf(a, b);
-          }
-        }
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float wave_total(float v) {  // fixed butterfly order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// The inverse normalisation of decode_latent_ens fused into the load (rollout entry point): (v / target_std) * sd + mn, every
-// operation rounded on its own as chan_affine_kernel (layout.hip) and track_gather_kernel (track.hip) round theirs - those files are
-// built with -ffp-contract=off, this one is not, so the contraction is switched off here.  x / 1 == x: the division is skipped
-// for the default target_std.
-struct InvNorm {
-  float target_std, sd, mn;
-  bool unit;  // target_std == 1
-};
-
-__device__ __forceinline__ float inv_norm(float v, const InvNorm& n) {
-#pragma clang fp contract(off)
-  const float q = n.unit ? v : v / n.target_std;
-  const float m = q * n.sd;
-  return m + n.mn;
-}
 
 // One grid point of one (channel, lead time): the M member loads, sort, skill / spread / crps / se, the ACC terms, the validity flags
 // and the fixed-order workgroup reduction of the 15 partial sums into part_dst[NQ + 7].  f / tp / clp point at this thread's point
@@ -183,7 +136,7 @@ __device__ __forceinline__ void score_point(const float* f, long long ms, int M,
   const int wave = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < NR; ++i) {
-    const float t_ = wave_total(v[i]);
+    const float t_ = wave_sum(v[i]);
     if ((threadIdx.x & 63) == 0) red[wave][i] = t_;
   }
   __syncthreads();
@@ -237,7 +190,7 @@ __global__ __launch_bounds__(TPB) void rollout_scores_kernel(RolloutArgs a) {
   const float* tp = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs + pp;
   const float* clp = a.clim ? a.clim + static_cast<long long>(a.cl_slot[l]) * a.cl_ss + static_cast<long long>(c) * a.cl_cs + pp : nullptr;
   InvNorm nrm{};
-  if constexpr (INV) nrm = InvNorm{a.target_std, a.sd[c], a.mean[c], a.target_std == 1.0f};
+  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
   score_point<NP, NUSE, INV, SINGLE>(f, a.fc_ms, a.M, tp, clp, a.lat_w + pp / a.W, in, nullptr, nullptr,
                                      a.part + ((static_cast<long long>(l) * a.C + c) * a.nblk + blockIdx.x) * nrec(SINGLE), nrm);
 }
@@ -259,7 +212,7 @@ __device__ __forceinline__ void finish_point(const float* __restrict__ part, int
     for (int i = 0; i < NR; ++i) s[i] += src[i];
   }
 #pragma unroll
-  for (int i = 0; i < NR; ++i) s[i] = wave_total(s[i]);
+  for (int i = 0; i < NR; ++i) s[i] = wave_sum(s[i]);
   if (threadIdx.x != 0) return;
   const float nanv = __builtin_nanf("");
   const float total = s[NR - 1];
@@ -346,14 +299,9 @@ extern "C" int ldc_ensemble_scores(const float* forecast, long long member_strid
   a.nblk = static_cast<int>(ldc_cdiv(static_cast<long long>(H) * W, TPB));
   dim3 grid(a.nblk, C);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (M <= 8) hipLaunchKernelGGL((ensemble_scores_kernel<8, 8>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 16) hipLaunchKernelGGL((ensemble_scores_kernel<16, 16>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 24) hipLaunchKernelGGL((ensemble_scores_kernel<32, 24>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 32) hipLaunchKernelGGL((ensemble_scores_kernel<32, 32>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 40) hipLaunchKernelGGL((ensemble_scores_kernel<64, 40>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 48) hipLaunchKernelGGL((ensemble_scores_kernel<64, 48>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 56) hipLaunchKernelGGL((ensemble_scores_kernel<64, 56>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((ensemble_scores_kernel<64, 64>), grid, dim3(TPB), 0, s, a);
+  ldc_dispatch_sort_arm(M, [&](auto np, auto nuse) {
+    hipLaunchKernelGGL((ensemble_scores_kernel<decltype(np)::value, decltype(nuse)::value>), grid, dim3(TPB), 0, s, a);
+  });
   int st = ldc_launch_status();
   if (st != LDC_OK) return st;
   hipLaunchKernelGGL(ensemble_scores_finish_kernel, dim3(C), dim3(64), 0, s, a.part, a.nblk, C, nan_channel,
@@ -369,15 +317,9 @@ extern "C" long long ldc_rollout_scores_workspace_bytes(int C, int L, int H, int
 namespace {
 template <bool INV, bool SINGLE = false>
 void launch_rollout(const RolloutArgs& a, dim3 grid, hipStream_t s) {
-  const int M = a.M;
-  if (M <= 8) hipLaunchKernelGGL((rollout_scores_kernel<8, 8, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 16) hipLaunchKernelGGL((rollout_scores_kernel<16, 16, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 24) hipLaunchKernelGGL((rollout_scores_kernel<32, 24, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 32) hipLaunchKernelGGL((rollout_scores_kernel<32, 32, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 40) hipLaunchKernelGGL((rollout_scores_kernel<64, 40, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 48) hipLaunchKernelGGL((rollout_scores_kernel<64, 48, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 56) hipLaunchKernelGGL((rollout_scores_kernel<64, 56, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((rollout_scores_kernel<64, 64, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
+  ldc_dispatch_sort_arm(a.M, [&](auto np, auto nuse) {
+    hipLaunchKernelGGL((rollout_scores_kernel<decltype(np)::value, decltype(nuse)::value, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
+  });
 }
 }  // namespace
 
@@ -394,9 +336,7 @@ extern "C" int ldc_rollout_scores(const float* forecast, long long member_stride
   LDC_CHECK_PTR(out);
   LDC_CHECK_PTR(workspace);
   if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
-  if (mean != nullptr) LDC_CHECK_PTR(std_);
-  if (M <= 0 || C <= 0 || L <= 0 || H <= 0 || W <= 0 || L_total <= 0 || l_off < 0) return LDC_ERR_ARG;
-  if (static_cast<long long>(l_off) + L > L_total) return LDC_ERR_ARG;
+  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (M > 64 || C > 65535 || L > 65535) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_scores_workspace_bytes(C, L, H, W)) return LDC_ERR_ARG;
   RolloutArgs a{};
@@ -444,9 +384,7 @@ extern "C" int ldc_validation_scores(const float* forecast, long long member_str
   LDC_CHECK_PTR(lat_weight);
   LDC_CHECK_PTR(out);
   LDC_CHECK_PTR(workspace);
-  if (mean != nullptr) LDC_CHECK_PTR(std_);
-  if (M <= 0 || C <= 0 || L <= 0 || H <= 0 || W <= 0 || L_total <= 0 || l_off < 0) return LDC_ERR_ARG;
-  if (static_cast<long long>(l_off) + L > L_total) return LDC_ERR_ARG;
+  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (M > 64 || C > 65535 || L > 65535) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_validation_scores_workspace_bytes(C, L, H, W)) return LDC_ERR_ARG;
   RolloutArgs a{};

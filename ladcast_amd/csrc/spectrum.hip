@@ -1,8 +1,8 @@
 // Zonal power spectra of a decoded ensemble: power per longitudinal wavenumber of the members, of the ensemble
 // mean and of the truth, per (channel, lead time).  Not in the reference (ladcast/evaluate/utils.py stops at CRPS and ACC).
 // Addressing is that of ldc_rollout_reliability (reliability.hip): forecast by member / lead / channel strides, optional fused inverse
-// normalisation, truth as a table of planes with a slot per lead time, output columns at l_off.  row_weight[H] >= 0 replaces the latitude
-// weight: a row whose weight is not > 0 is never read.
+// normalisation (inv_norm, ensemble_common.h), truth as a table of planes with a slot per lead time, output columns at l_off.
+// row_weight[H] >= 0 replaces the latitude weight: a row whose weight is not > 0 is never read.
 // Per row of W points (half = W / 2, K = half + 1 bins), for each of the M + 2 sequences y (members in order, ensemble mean m, truth t):
 //   mu  = (sum_j y_j) / W                 pair sums y_p + y_{W-p} per lane in index order, wave butterfly
 //   e_p = (y_p - mu) + (y_{W-p} - mu), o_p = (y_p - mu) - (y_{W-p} - mu) for 0 < p < half;  e_0 = y_0 - mu, e_half = y_half - mu, o = 0
@@ -18,7 +18,7 @@
 // Built with -ffp-contract=off: the only fused operations are the explicit fmaf of the transform.
 #include <math.h>
 
-#include "common.h"
+#include "ensemble_common.h"
 
 namespace {
 
@@ -46,18 +46,6 @@ struct SpecArgs {
   int nrec;
 };
 
-// the inverse normalisation of reliability.hip / ldc_chan_affine(inverse=1): (v / target_std) * sd + mn, each operation rounded on its own
-struct InvNorm {
-  float target_std, sd, mn;
-  bool unit;
-};
-
-__device__ __forceinline__ float inv_norm(float v, const InvNorm& n) {
-  const float q = n.unit ? v : v / n.target_std;
-  const float m = q * n.sd;
-  return m + n.mn;
-}
-
 __global__ void spectrum_table_kernel(float2* __restrict__ table, int W) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= W) return;
@@ -81,7 +69,7 @@ __global__ __launch_bounds__(WAVE) void spectrum_kernel(SpecArgs a) {
   const float* fbase = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs;
   const float* tbase = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs;
   InvNorm nrm{};
-  if constexpr (INV) nrm = InvNorm{a.target_std, a.sd[c], a.mean[c], a.target_std == 1.0f};
+  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
   for (int i = t; i < W; i += WAVE) s_tw[i] = a.table[i];
   int kk[KB];  // the lane's bins; 0: none (the table's entry 0 is read, nothing is kept)
 #pragma unroll
@@ -316,9 +304,7 @@ extern "C" int ldc_rollout_spectrum(const float* forecast, long long member_stri
   LDC_CHECK_PTR(out);
   LDC_CHECK_PTR(n_invalid);
   LDC_CHECK_PTR(workspace);
-  if (mean != nullptr) LDC_CHECK_PTR(std_);
-  if (M <= 0 || C <= 0 || L <= 0 || H <= 0 || W <= 0 || L_total <= 0 || l_off < 0) return LDC_ERR_ARG;
-  if (static_cast<long long>(l_off) + L > L_total) return LDC_ERR_ARG;
+  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (!served(M, C, L, H, W)) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_spectrum_workspace_bytes(M, C, L, H, W)) return LDC_ERR_ARG;
   LDC_CHECK_ALIGN16(workspace);

@@ -131,6 +131,53 @@ def _plane_table(t: torch.Tensor, slots, C: int, L: int, H: int, W: int, what: s
     return t, t.stride(0), t.stride(1), slots
 
 
+# What the five rollout_* / validation_scores wrappers below share.  Each wrapper runs every check that needs no device first (ValueError,
+# NotImplementedError), then asks for the device (`hip._dev`) with the tensors it cannot take from the host, then allocates and launches.
+def _forecast_view(forecast: torch.Tensor, lead_dim: int):
+    """-> (f, M, C, L, H, W): the forecast as (ens, C, L, H, W) with a contiguous (H, W) plane, any member / lead / channel strides"""
+    if forecast.dim() != 5 or lead_dim not in (0, 2):
+        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
+    if forecast.dtype != torch.float32:
+        raise NotImplementedError("fp32 only")
+    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
+    if f.stride(-1) != 1 or f.stride(-2) != f.shape[-1]:
+        f = f.contiguous()
+    return (f, *f.shape)
+
+
+def _channel_affine(mean, std, C: int, dev):
+    """`mean` / `std` of the fused inverse normalisation -> two contiguous fp32 (C,) vectors on `dev`, or (None, None)"""
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is None:
+        return None, None
+    if mean.numel() != C or std.numel() != C:
+        raise ValueError(f"mean / std must hold one value per channel ({C})")
+    return mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
+
+
+def _row_weight(w: torch.Tensor, H: int, dev, what: str) -> torch.Tensor:
+    """`lat_weight` / `row_weight` -> a contiguous fp32 (H,) vector on `dev`"""
+    if w.numel() != H:
+        raise ValueError(f"{what} must have one value per latitude row")
+    return w.to(dev, torch.float32).reshape(-1).contiguous()
+
+
+def _upload_slots(slots, dev) -> torch.Tensor:
+    """a host list of ints (or a list of such lists) -> an int32 device tensor, without stalling the host"""
+    return hip.upload_nonblocking(torch.tensor(slots, dtype=torch.int32), dev)
+
+
+def _score_buffer(out, n: int, C: int, dev, who: str):
+    """the contiguous (n, C, L_total) fp32 buffer behind `out`, the dict an earlier call of `who` returned; None when there is no `out`"""
+    if out is None:
+        return None
+    buf = getattr(out, "_buffer", None) if not isinstance(out, torch.Tensor) else out
+    if buf is None or buf.dim() != 3 or buf.shape[:2] != (n, C) or not buf.is_contiguous() or buf.dtype != torch.float32 or buf.device != dev:
+        raise ValueError(f"out must be the dict an earlier {who} call returned (or its contiguous ({n}, C, L_total) fp32 buffer)")
+    return buf
+
+
 @torch.no_grad()
 def rollout_scores(forecast: torch.Tensor, truth: torch.Tensor, clim: Optional[torch.Tensor], lat_weight: torch.Tensor, sst_channel: int, *,
                    lead_dim: int = 2, mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, target_std: float = 1.0,
@@ -147,38 +194,20 @@ def rollout_scores(forecast: torch.Tensor, truth: torch.Tensor, clim: Optional[t
     climatology); clim None = no ACC; they are never transformed.  Returns the dict of five (C, L_total) device tensors under
     `ensemble_scores`' names: a fresh one (L_total = lead_offset + L, unwritten columns NaN), or `out` - the dict an earlier call
     returned - of which columns lead_offset .. lead_offset + L - 1 are written."""
-    hip._dev(forecast, truth, clim, lat_weight, mean, std)
-    if forecast.dim() != 5 or lead_dim not in (0, 2):
-        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
-    if forecast.dtype != torch.float32:
-        raise NotImplementedError("fp32 only")
-    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
-    M, C, L, H, W = f.shape
-    if f.stride(-1) != 1 or f.stride(-2) != W:
-        f = f.contiguous()
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
     dev = f.device
     t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slots, C, L, H, W, "truth")
     c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
-    w = lat_weight.to(dev, torch.float32).reshape(-1).contiguous()
-    if w.numel() != H:
-        raise ValueError("lat_weight must have one value per latitude row")
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std go together")
-    if mean is not None:
-        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
-        if mean.numel() != C or std.numel() != C:
-            raise ValueError(f"mean / std must hold one value per channel ({C})")
-    if out is None:
-        buf = torch.full((5, C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
-    else:
-        buf = getattr(out, "_buffer", None) if not isinstance(out, torch.Tensor) else out
-        if buf is None or buf.dim() != 3 or buf.shape[:2] != (5, C) or not buf.is_contiguous() or buf.dtype != torch.float32 or buf.device != dev:
-            raise ValueError("out must be the dict an earlier rollout_scores call returned (or its contiguous (5, C, L_total) fp32 buffer)")
-    slots = torch.tensor([t_slots, c_slots if c_slots is not None else t_slots], dtype=torch.int32)
-    slots = hip.upload_nonblocking(slots, dev)
+    w = _row_weight(lat_weight, H, dev, "lat_weight")
+    mn, sd = _channel_affine(mean, std, C, dev)
+    buf = _score_buffer(out, len(SCORE_NAMES), C, dev, "rollout_scores")
+    hip._dev(forecast, truth, clim, lat_weight, mean, std)
+    if buf is None:
+        buf = torch.full((len(SCORE_NAMES), C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
+    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], dev)
     hip.rollout_scores(f, t, slots[0], c, None if c is None else slots[1], w, buf, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0),
                        lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs,
-                       clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mean, std=std, target_std=target_std, nan_channel=sst_channel,
+                       clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mn, std=sd, target_std=target_std, nan_channel=sst_channel,
                        L_total=buf.shape[2], l_off=lead_offset)
     return ScoreDict(buf)
 
@@ -206,36 +235,18 @@ def validation_scores(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: t
     forecast, `lead_dim`, `mean` / `std` / `target_std`, truth / `truth_slots`, `out` / `lead_offset`: as `rollout_scores`.  Returns the
     dict of three (C, L_total) device tensors over one contiguous (3, C, L_total) buffer (`VALIDATION_SCORE_NAMES`); unwritten columns of
     a fresh one are NaN."""
-    hip._dev(forecast, truth, lat_weight, mean, std)
-    if forecast.dim() != 5 or lead_dim not in (0, 2):
-        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
-    if forecast.dtype != torch.float32:
-        raise NotImplementedError("fp32 only")
-    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
-    M, C, L, H, W = f.shape
-    if f.stride(-1) != 1 or f.stride(-2) != W:
-        f = f.contiguous()
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
     dev = f.device
     t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slots, C, L, H, W, "truth")
-    w = lat_weight.to(dev, torch.float32).reshape(-1).contiguous()
-    if w.numel() != H:
-        raise ValueError("lat_weight must have one value per latitude row")
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std go together")
-    if mean is not None:
-        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
-        if mean.numel() != C or std.numel() != C:
-            raise ValueError(f"mean / std must hold one value per channel ({C})")
-    n = len(VALIDATION_SCORE_NAMES)
-    if out is None:
-        buf = torch.full((n, C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
-    else:
-        buf = getattr(out, "_buffer", None) if not isinstance(out, torch.Tensor) else out
-        if buf is None or buf.dim() != 3 or buf.shape[:2] != (n, C) or not buf.is_contiguous() or buf.dtype != torch.float32 or buf.device != dev:
-            raise ValueError(f"out must be the dict an earlier validation_scores call returned (or its contiguous ({n}, C, L_total) fp32 buffer)")
-    slots = hip.upload_nonblocking(torch.tensor(t_slots, dtype=torch.int32), dev)
+    w = _row_weight(lat_weight, H, dev, "lat_weight")
+    mn, sd = _channel_affine(mean, std, C, dev)
+    buf = _score_buffer(out, len(VALIDATION_SCORE_NAMES), C, dev, "validation_scores")
+    hip._dev(forecast, truth, lat_weight, mean, std)
+    if buf is None:
+        buf = torch.full((len(VALIDATION_SCORE_NAMES), C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
+    slots = _upload_slots(t_slots, dev)
     hip.validation_scores(f, t, slots, w, buf, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
-                          channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
+                          channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mn, std=sd,
                           target_std=target_std, L_total=buf.shape[2], l_off=lead_offset)
     return ScoreDict(buf, VALIDATION_SCORE_NAMES)
 
@@ -278,32 +289,16 @@ def rollout_reliability(forecast: torch.Tensor, truth: torch.Tensor, lat_weight:
     forecast, `lead_dim`, `mean` / `std` / `target_std`: as `rollout_scores`.  truth: (C, L, H, W), or with `truth_slot` (one host int
     per lead time) an (N, C, H, W) table.  Returns a dict of device tensors with L_total = l_off + L columns (unwritten columns: NaN, empty
     histograms), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call returned."""
-    hip._dev(forecast, truth, lat_weight, mean, std)
-    if forecast.dim() != 5 or lead_dim not in (0, 2):
-        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
-    if forecast.dtype != torch.float32:
-        raise NotImplementedError("fp32 only")
-    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
-    M, C, L, H, W = f.shape
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
     if not 1 <= M <= MAX_RELIABILITY_MEMBERS:
         raise ValueError(f"{M} members: ldc_rollout_reliability serves 1 .. {MAX_RELIABILITY_MEMBERS}")
-    if f.stride(-1) != 1 or f.stride(-2) != W:
-        f = f.contiguous()
     dev = f.device
     t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    w = lat_weight.to(dev, torch.float32).reshape(-1).contiguous()
-    if w.numel() != H:
-        raise ValueError("lat_weight must have one value per latitude row")
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std go together")
-    if mean is not None:
-        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
-        if mean.numel() != C or std.numel() != C:
-            raise ValueError(f"mean / std must hold one value per channel ({C})")
+    w = _row_weight(lat_weight, H, dev, "lat_weight")
+    mn, sd = _channel_affine(mean, std, C, dev)
     n = len(RELIABILITY_NAMES)
-    if out is None:
-        bufs = empty_reliability(M, C, l_off + L, dev)._buffers
-    else:
+    bufs = None
+    if out is not None:
         bufs = getattr(out, "_buffers", None)
         ok = bufs is not None and bufs[0].dim() == 3 and bufs[0].shape[:2] == (n, C) and all(b.is_contiguous() and b.device == dev for b in bufs)
         if ok:
@@ -311,9 +306,12 @@ def rollout_reliability(forecast: torch.Tensor, truth: torch.Tensor, lat_weight:
             ok = bufs[1].shape == (C, Lt, M + 1) and bufs[2].shape == (C, Lt, M + 1) and bufs[3].shape == (C, Lt)
         if not ok:
             raise ValueError("out must be the dict an earlier rollout_reliability call returned for the same ensemble size and channels")
-    slots = hip.upload_nonblocking(torch.tensor(t_slots, dtype=torch.int32), dev)
+    hip._dev(forecast, truth, lat_weight, mean, std)
+    if bufs is None:
+        bufs = empty_reliability(M, C, l_off + L, dev)._buffers
+    slots = _upload_slots(t_slots, dev)
     hip.rollout_reliability(f, t, slots, w, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
-                            channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
+                            channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mn, std=sd,
                             target_std=target_std, nan_channel=sst_channel, L_total=bufs[0].shape[2], l_off=l_off)
     return ReliabilityDict(*bufs)
 
@@ -356,44 +354,31 @@ def rollout_spectrum(forecast: torch.Tensor, truth: torch.Tensor, row_weight: to
     caller's responsibility: the kernel treats a weight that is not > 0 as 0.  forecast, `lead_dim`, `mean` / `std` / `target_std`, truth /
     `truth_slot`, `out` / `l_off`: as `rollout_reliability`.  Returns a dict of device tensors with L_total = l_off + L columns (unwritten
     columns: NaN, `n_invalid` 0), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_spectrum`) returned."""
-    if forecast.dim() != 5 or lead_dim not in (0, 2):
-        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
-    if forecast.dtype != torch.float32:
-        raise NotImplementedError("fp32 only")
-    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
-    M, C, L, H, W = f.shape
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
     if W % 2 or not MIN_SPECTRUM_W <= W <= MAX_SPECTRUM_W:
         raise ValueError(f"{W} points per row: ldc_rollout_spectrum serves even W in {MIN_SPECTRUM_W} .. {MAX_SPECTRUM_W}")
     if not 1 <= M <= MAX_SPECTRUM_MEMBERS:
         raise ValueError(f"{M} members: ldc_rollout_spectrum serves 1 .. {MAX_SPECTRUM_MEMBERS}")
-    if row_weight.numel() != H:
-        raise ValueError("row_weight must have one value per latitude row")
+    dev = f.device
+    w = _row_weight(row_weight, H, dev, "row_weight")
     if not row_weight.is_cuda and not bool((row_weight >= 0).all()):  # NaN fails the comparison too
         raise ValueError("row_weight must be non-negative (0 leaves a row out) and not NaN")
-    hip._dev(forecast, truth, mean, std)
-    if f.stride(-1) != 1 or f.stride(-2) != W:
-        f = f.contiguous()
-    dev = f.device
     t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    w = row_weight.to(dev, torch.float32).reshape(-1).contiguous()
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std go together")
-    if mean is not None:
-        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
-        if mean.numel() != C or std.numel() != C:
-            raise ValueError(f"mean / std must hold one value per channel ({C})")
+    mn, sd = _channel_affine(mean, std, C, dev)
     n, K = len(SPECTRUM_NAMES), W // 2 + 1
-    if out is None:
-        bufs = empty_spectrum(C, l_off + L, W, dev)._buffers
-    else:
+    bufs = None
+    if out is not None:
         bufs = getattr(out, "_buffers", None)
         ok = bufs is not None and len(bufs) == 2 and bufs[0].dim() == 4 and bufs[0].shape[:2] == (n, C) and bufs[0].shape[3] == K \
             and bufs[0].dtype == torch.float32 and bufs[1].dtype == torch.int32 and all(b.is_contiguous() and b.device == dev for b in bufs)
         if not (ok and bufs[1].shape == (C, bufs[0].shape[2])):
             raise ValueError("out must be the dict an earlier rollout_spectrum call (or empty_spectrum) returned for the same channels and W")
-    slots = hip.upload_nonblocking(torch.tensor(t_slots, dtype=torch.int32), dev)
+    hip._dev(forecast, truth, mean, std)
+    if bufs is None:
+        bufs = empty_spectrum(C, l_off + L, W, dev)._buffers
+    slots = _upload_slots(t_slots, dev)
     hip.rollout_spectrum(f, t, slots, w, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
-                         channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mean, std=std,
+                         channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mn, std=sd,
                          target_std=target_std, L_total=bufs[0].shape[2], l_off=l_off)
     return SpectrumDict(*bufs)
 
@@ -441,12 +426,7 @@ def rollout_products(forecast: torch.Tensor, *, quantiles=(), thresholds=None, t
     indexed by the original channel.  `stats=False` leaves mean / std / min / max out.  forecast, `lead_dim`, `mean` / `std` /
     `target_std`: as `rollout_scores`.  Returns a `ProductsDict` of device views with L_total = l_off + L columns (unwritten columns NaN),
     or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_products`) returned."""
-    if forecast.dim() != 5 or lead_dim not in (0, 2):
-        raise ValueError("forecast must be (ens, C, L, H, W), or (L, ens, C, H, W) with lead_dim=0")
-    if forecast.dtype != torch.float32:
-        raise NotImplementedError("fp32 only")
-    f = forecast if lead_dim == 2 else forecast.permute(1, 2, 0, 3, 4)
-    M, C, L, H, W = f.shape
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
     qs = [float(q) for q in (quantiles.tolist() if isinstance(quantiles, torch.Tensor) else quantiles)]
     if not 1 <= M <= MAX_PRODUCT_MEMBERS:
         raise ValueError(f"{M} members: ldc_rollout_products serves 1 .. {MAX_PRODUCT_MEMBERS}")
@@ -476,16 +456,9 @@ def rollout_products(forecast: torch.Tensor, *, quantiles=(), thresholds=None, t
     if l_off < 0:
         raise ValueError("l_off must not be negative")
     dev = f.device
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std go together")
-    if mean is not None:
-        mean, std = mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
-        if mean.numel() != C or std.numel() != C:
-            raise ValueError(f"mean / std must hold one value per channel ({C})")
-    if out is None:
-        hip._dev(forecast)
-        bufs = empty_products(Cs, l_off + L, H, W, dev, n_quantiles=Q, n_thresholds=P, stats=stats)._buffers
-    else:
+    mn, sd = _channel_affine(mean, std, C, dev)
+    bufs = None
+    if out is not None:
         bufs = getattr(out, "_buffers", None)
         ok = bufs is not None and len(bufs) == 3
         if ok:
@@ -500,13 +473,13 @@ def rollout_products(forecast: torch.Tensor, *, quantiles=(), thresholds=None, t
             raise ValueError("out must be the dict an earlier rollout_products call (or empty_products) returned for the same channels, "
                              "quantiles, thresholds and grid, with room for columns l_off .. l_off + L - 1")
     hip._dev(forecast)
-    if f.stride(-1) != 1 or f.stride(-2) != W:
-        f = f.contiguous()
+    if bufs is None:
+        bufs = empty_products(Cs, l_off + L, H, W, dev, n_quantiles=Q, n_thresholds=P, stats=stats)._buffers
     st, qu, ex = (b if n else None for b, n in zip(bufs, (stats, Q, P)))
     L_total = next(b.shape[2] for b in (st, qu, ex) if b is not None)
-    chan_d = None if chan is None else hip.upload_nonblocking(torch.tensor(chan, dtype=torch.int32), dev)
+    chan_d = None if chan is None else _upload_slots(chan, dev)
     thr_d = None if P == 0 else (thresholds if thresholds.is_cuda else hip.upload_nonblocking(thresholds.contiguous(), dev)).contiguous()
     hip.rollout_products(f, desc, M=M, C=C, Cs=Cs, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2), channel_stride=f.stride(1),
-                         channels=chan_d, thr=thr_d, stats=st, quant=qu, exceed=ex, mean=mean, std=std, target_std=target_std, L_total=L_total,
+                         channels=chan_d, thr=thr_d, stats=st, quant=qu, exceed=ex, mean=mn, std=sd, target_std=target_std, L_total=L_total,
                          l_off=l_off)
     return ProductsDict(*bufs)

@@ -391,6 +391,16 @@ def ensemble_scores(forecast, truth, clim, lat_weight, out, *, M, C, H, W, membe
                                    _p(ws), ws.numel() * 4, _stream()), "ldc_ensemble_scores")
 
 
+def _forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std):
+    """the leading arguments of ldc_rollout_scores / _reliability / _spectrum / _products and ldc_validation_scores"""
+    return _p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std)
+
+
+def _truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot):
+    """the truth table that follows them in every one of these but ldc_rollout_products"""
+    return _p(truth), truth_slot_stride, truth_channel_stride, _p(truth_slot)
+
+
 def rollout_scores(forecast, truth, truth_slot, clim, clim_slot, lat_weight, out, *, M, C, L, H, W, member_stride, lead_stride, channel_stride,
                    truth_slot_stride, truth_channel_stride, clim_slot_stride=0, clim_channel_stride=0, mean=None, std=None, target_std=1.0,
                    nan_channel=-1, L_total, l_off=0):
@@ -398,10 +408,10 @@ def rollout_scores(forecast, truth, truth_slot, clim, clim_slot, lat_weight, out
     (ladcast_hip.h: ldc_rollout_scores); truth_slot / clim_slot: device int32 [L]"""
     _dev(forecast, truth, truth_slot, clim, clim_slot, lat_weight, out, mean, std)
     ws = _workspace("rollout_scores", forecast.device, int(lib.ldc_rollout_scores_workspace_bytes(C, L, H, W)), grow=True)
-    _check(lib.ldc_rollout_scores(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
-                                  truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(clim), clim_slot_stride, clim_channel_stride,
-                                  _p(clim_slot), _p(lat_weight), M, C, L, H, W, nan_channel, _p(out), L_total, l_off, _p(ws), ws.numel() * 4,
-                                  _stream()), "ldc_rollout_scores")
+    _check(lib.ldc_rollout_scores(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                  *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
+                                  clim_channel_stride, _p(clim_slot), _p(lat_weight), M, C, L, H, W, nan_channel, _p(out), L_total, l_off, _p(ws),
+                                  ws.numel() * 4, _stream()), "ldc_rollout_scores")
 
 
 def validation_scores(forecast, truth, truth_slot, lat_weight, out, *, M, C, L, H, W, member_stride, lead_stride, channel_stride,
@@ -410,9 +420,9 @@ def validation_scores(forecast, truth, truth_slot, lat_weight, out, *, M, C, L, 
     (ladcast_hip.h: ldc_validation_scores); truth_slot: device int32 [L]"""
     _dev(forecast, truth, truth_slot, lat_weight, out, mean, std)
     ws = _workspace("validation_scores", forecast.device, int(lib.ldc_validation_scores_workspace_bytes(C, L, H, W)), grow=True)
-    _check(lib.ldc_validation_scores(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
-                                     truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(lat_weight), M, C, L, H, W, _p(out), L_total,
-                                     l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_validation_scores")
+    _check(lib.ldc_validation_scores(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                     *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(lat_weight), M, C, L, H, W,
+                                     _p(out), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_validation_scores")
 
 
 def rollout_reliability(forecast, truth, truth_slot, lat_weight, out, hist_count, hist_weight, n_invalid, *, M, C, L, H, W, member_stride,
@@ -423,10 +433,10 @@ def rollout_reliability(forecast, truth, truth_slot, lat_weight, out, hist_count
     _dev(forecast, truth, truth_slot, lat_weight, out, hist_count, hist_weight, n_invalid, mean, std)
     nbytes = int(lib.ldc_rollout_reliability_workspace_bytes(M, C, L, H, W))
     ws = _workspace("rollout_reliability", forecast.device, max(nbytes, 4), grow=True)
-    _check(lib.ldc_rollout_reliability(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
-                                       truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(lat_weight), M, C, L, H, W, nan_channel,
-                                       _p(out), _p(hist_count), _p(hist_weight), _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4,
-                                       _stream()), "ldc_rollout_reliability")
+    _check(lib.ldc_rollout_reliability(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                       *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(lat_weight), M, C, L, H, W,
+                                       nan_channel, _p(out), _p(hist_count), _p(hist_weight), _p(n_invalid), L_total, l_off, _p(ws),
+                                       ws.numel() * 4, _stream()), "ldc_rollout_reliability")
 
 
 def rollout_spectrum(forecast, truth, truth_slot, row_weight, out, n_invalid, *, M, C, L, H, W, member_stride, lead_stride, channel_stride,
@@ -436,9 +446,9 @@ def rollout_spectrum(forecast, truth, truth_slot, row_weight, out, n_invalid, *,
     _dev(forecast, truth, truth_slot, row_weight, out, n_invalid, mean, std)
     nbytes = int(lib.ldc_rollout_spectrum_workspace_bytes(M, C, L, H, W))
     ws = _workspace("rollout_spectrum", forecast.device, max(nbytes, 4), grow=True)
-    _check(lib.ldc_rollout_spectrum(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(truth),
-                                    truth_slot_stride, truth_channel_stride, _p(truth_slot), _p(row_weight), M, C, L, H, W, _p(out),
-                                    _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_spectrum")
+    _check(lib.ldc_rollout_spectrum(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                    *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(row_weight), M, C, L, H, W,
+                                    _p(out), _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_spectrum")
 
 
 def products_desc(quantiles, M, threshold_dirs=()):
@@ -472,9 +482,9 @@ def rollout_products(forecast, desc, *, M, C, L, H, W, member_stride, lead_strid
     l_off .. l_off + L - 1 of L lead times in one launch, each output optional (ladcast_hip.h: ldc_rollout_products); desc:
     `products_desc`; channels: device int32 [Cs] or None (all); thr: device fp32 [P][Cs]"""
     _dev(forecast, channels, thr, stats, quant, exceed, mean, std)
-    _check(lib.ldc_rollout_products(_p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std), _p(channels),
-                                    M, C, C if Cs is None else Cs, L, H, W, ctypes.byref(desc), _p(thr), _p(stats), _p(quant), _p(exceed),
-                                    L_total, l_off, _stream()), "ldc_rollout_products")
+    _check(lib.ldc_rollout_products(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                    _p(channels), M, C, C if Cs is None else Cs, L, H, W, ctypes.byref(desc), _p(thr), _p(stats), _p(quant),
+                                    _p(exceed), L_total, l_off, _stream()), "ldc_rollout_products")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):

@@ -44,11 +44,11 @@ TPB = 256
 KEYS = ("ens_acc", "ens_mse", "crps_spread", "crps_skill", "crps")
 VKEYS = ("ens_mse", "single_mse", "crps")
 FLT_MAX_BITS = 0x7F7FFFFF  # the largest finite fp32: the poison of guarded INPUTS (NaN is a legal input of these kernels)
-ARMS = ((8, 8), (16, 16), (32, 24), (32, 32), (64, 40), (64, 48), (64, 56), (64, 64))  # sort_network<NP, NUSE>
+ARMS = ((8, 8), (16, 16), (32, 24), (32, 32), (64, 40), (64, 48), (64, 56), (64, 64))  # ldc_dispatch_sort_arm (csrc/ensemble_common.h)
 
 
 def sort_arm(M):
-    """(NP, NUSE) the dispatch of scoring.hip picks for M members"""
+    """(NP, NUSE) that ldc_dispatch_sort_arm (csrc/ensemble_common.h) picks for M members"""
     return next(a for a in ARMS if M <= a[1])
 
 

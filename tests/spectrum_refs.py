@@ -59,7 +59,7 @@ def s_k(W):
 
 
 def inv_norm_f32(v, mean, std, target_std):
-    """(v / target_std) * std[c] + mean[c] on the channel axis 1, every operation rounded to fp32 (spectrum.hip: inv_norm)"""
+    """(v / target_std) * std[c] + mean[c] on the channel axis 1, every operation rounded to fp32 (csrc/ensemble_common.h: inv_norm)"""
     shape = [1, -1] + [1] * (v.ndim - 2)
     q = v.astype(f32) if target_std == 1.0 else (v.astype(f32) / f32(target_std)).astype(f32)
     return ((q * std.astype(f32).reshape(shape)).astype(f32) + mean.astype(f32).reshape(shape)).astype(f32)

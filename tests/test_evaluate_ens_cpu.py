@@ -127,3 +127,48 @@ def test_lat_weights():
     w48 = EG.lat_weights_for(48)
     lat48 = np.linspace(-90, 90, 49)[1:]
     assert w48.shape == (48,) and np.allclose(w48.numpy(), np.cos(np.deg2rad(lat48)) / np.cos(np.deg2rad(lat48)).mean(), rtol=1e-6, atol=1e-7)
+
+
+# ---- the forecast view the five rollout wrappers share: one exception per mistake, before the device is asked for -----------------------------
+_M, _C, _L, _H, _W = 2, 1, 1, 3, 8
+_WRAPPERS = ("rollout_scores", "validation_scores", "rollout_reliability", "rollout_spectrum", "rollout_products")
+
+
+def _wrapper_call(name, *, forecast=None, weight=None, **kw):
+    """`name` on host tensors of shape (2, 1, 1, 3, 8), valid but for what the caller replaces"""
+    import torch
+
+    from ladcast_amd import evaluate as E
+
+    x = torch.zeros(_M, _C, _L, _H, _W) if forecast is None else forecast
+    t, w = torch.zeros(_C, _L, _H, _W), torch.ones(_H) if weight is None else weight
+    if name == "rollout_scores":
+        return E.rollout_scores(x, t, t.clone(), w, -1, **kw)
+    if name == "rollout_reliability":
+        return E.rollout_reliability(x, t, w, -1, **kw)
+    if name == "rollout_products":
+        return E.rollout_products(x, **kw)
+    return getattr(E, name)(x, t, w, **kw)
+
+
+@pytest.mark.parametrize("name", _WRAPPERS)
+def test_rollout_wrappers_share_their_argument_errors(name):
+    import torch
+
+    cases = [
+        (dict(forecast=torch.zeros(_M, _C, _H, _W)), ValueError, r"forecast must be \(ens, C, L, H, W\)"),
+        (dict(lead_dim=1), ValueError, r"forecast must be \(ens, C, L, H, W\)"),
+        (dict(forecast=torch.zeros(_M, _C, _L, _H, _W, dtype=torch.float64)), NotImplementedError, "fp32 only"),
+        (dict(mean=torch.zeros(_C)), ValueError, "mean and std go together"),
+        (dict(mean=torch.zeros(_C + 1), std=torch.ones(_C + 1)), ValueError, r"mean / std must hold one value per channel \(1\)"),
+    ]
+    if name != "rollout_products":  # no weight there
+        what = "row_weight" if name == "rollout_spectrum" else "lat_weight"
+        cases.append((dict(weight=torch.ones(_H + 1)), ValueError, f"{what} must have one value per latitude row"))
+    for kw, exc, match in cases:
+        with pytest.raises(exc, match=match):
+            _wrapper_call(name, **kw)
+    with pytest.raises(RuntimeError, match="device tensors"):  # nothing wrong but the host tensors
+        _wrapper_call(name)
+    with pytest.raises(RuntimeError, match="device tensors"):
+        _wrapper_call(name, mean=torch.zeros(_C), std=torch.ones(_C))
