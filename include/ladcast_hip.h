@@ -667,6 +667,44 @@ int ldc_rollout_products(const float* forecast, long long member_stride, long lo
                          const float* mean, const float* std_, float target_std, const int* channels, int M, int C, int Cs, int L, int H,
                          int W, const ldc_products_desc* desc, const float* thr, float* stats, float* quant, float* exceed, int L_total,
                          int l_off, void* stream);
+/* Verification of threshold events for every lead time of a decode batch in one launch (additive under ABI 5; events.hip, DESIGN.md
+ * section 8.4): per (event, lead time) the joint histogram of "how many of the M members show the event" against "did the truth show
+ * it", counted and latitude-weighted - the sufficient statistic of the Brier score and its decomposition, the reliability diagram and
+ * the ROC curve (ladcast_amd.evaluate.event_scores derives them on the host).  Not in the reference.  Addressing of forecast, inverse
+ * normalisation (mean == NULL: physical units), truth table, lat_weight and output columns exactly as ldc_rollout_reliability; the
+ * optional climatology table (clim, clim_slot_stride, clim_channel_stride, clim_slot: a DEVICE int array [L]) exactly as
+ * ldc_rollout_scores.  1 <= M <= 1024.
+ * desc: HOST descriptor of the E = n_events <= LDC_EVENTS_MAX events, read and checked in full by the call.  Event e looks at channel
+ *   c = channel[e] of the C channels; several events may share a channel.
+ * Per grid point of event e, the members x_i in member order after the inverse normalisation, truth t, climatology a:
+ *   u_i = x_i, v = t                 (anomaly[e] == 0)
+ *   u_i = x_i - a, v = t - a         (anomaly[e] == 1: one fp32 subtraction each; needs clim)
+ *   n = #{i : u_i > thr[e]} in 0 .. M and o = (v > thr[e]) in {0, 1} for dir[e] == +1; `<` in place of `>` for dir[e] == -1
+ *   the point is valid when no member, not the truth and (anomaly[e] == 1) not the climatology is NaN; +-inf are ordinary ordered values
+ *   hist_count  [E][L_total][M + 1][2] int32: valid points per (n, o)
+ *   hist_weight [E][L_total][M + 1][2] fp32: sum of lat_weight over those points, in a fixed order
+ *   n_invalid   [E][L_total] int32: points left out
+ *   Columns l_off .. l_off + L - 1 of every output are written, the others left alone.  No float atomics: run-to-run bit-equal.
+ * workspace: ldc_rollout_events_workspace_bytes(M, E, L, H, W) bytes of device scratch (0 for arguments the call refuses).
+ * LDC_ERR_ARG: a null or non-positive argument, n_events outside 1 .. LDC_EVENTS_MAX, a channel outside 0 .. C - 1, a direction that is
+ * not +-1, an anomaly that is not 0 / 1, anomaly == 1 with clim == NULL, clim without clim_slot, a NaN threshold, l_off + L > L_total or
+ * a workspace that is too small; LDC_ERR_UNSUPPORTED: M > 1024, L > 65535 or H * W > 2^24.  Nothing is launched on an error. */
+#define LDC_EVENTS_MAX 32
+typedef struct ldc_events_desc {
+  int n_events;                /* E */
+  int channel[LDC_EVENTS_MAX]; /* index into the C channels */
+  int dir[LDC_EVENTS_MAX];     /* +1: value > thr, -1: value < thr */
+  int anomaly[LDC_EVENTS_MAX]; /* 1: value is x - clim (needs clim), 0: value is x */
+  float thr[LDC_EVENTS_MAX];   /* physical units (of the anomaly where anomaly == 1) */
+} ldc_events_desc;
+int ldc_sizeof_events_desc(void);
+long long ldc_rollout_events_workspace_bytes(int M, int E, int L, int H, int W);
+int ldc_rollout_events(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride, const float* mean,
+                       const float* std_, float target_std, const float* truth, long long truth_slot_stride,
+                       long long truth_channel_stride, const int* truth_slot, const float* clim, long long clim_slot_stride,
+                       long long clim_channel_stride, const int* clim_slot, const float* lat_weight, int M, int C, int L, int H, int W,
+                       const ldc_events_desc* desc, int* hist_count, float* hist_weight, int* n_invalid, int L_total, int l_off,
+                       void* workspace, long long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

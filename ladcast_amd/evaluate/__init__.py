@@ -1,4 +1,4 @@
-from .utils import (VALIDATION_SCORE_NAMES, empty_products, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
+from .utils import (EVENT_SCORE_NAMES, VALIDATION_SCORE_NAMES, Event, empty_events, empty_products, event_scores, rollout_events, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
                     get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_products, rollout_reliability, rollout_scores, rollout_spectrum,
                     validation_scores)
 
@@ -8,7 +8,7 @@ _DENOISE_NAMES = ("denoising_loss", "evaluate_denoising_loss", "push_forward_pla
 _PRODUCTS_NAMES = ("products_of_latent_rollout",)  # products', likewise
 __all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
            "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores", "rollout_spectrum",  # also runs
-           "validation_scores", "empty_products", "rollout_products", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES]  # as `python -m`
+           "validation_scores", "empty_products", "rollout_products", "EVENT_SCORE_NAMES", "Event", "empty_events", "event_scores", "rollout_events", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES]  # as `python -m`
 
 
 def __getattr__(name):

@@ -16,6 +16,11 @@ the south pole.  `--reliability` adds the spread-skill ratio and the rank histog
 `ens_var.npy`, `ssr.npy`, `n_invalid.npy` (init time, C, lead time) and `rank_hist.npy`, `rank_hist_weighted.npy` (C, lead time, ens + 1).  `--spectrum` adds the zonal power spectra of the members, the ensemble
 mean and the truth (`ldc_rollout_spectrum`, not in the reference): `spec_members.npy`, `spec_mean.npy`, `spec_truth.npy` (init time, C,
 lead time, W / 2 + 1) and `spec_n_invalid.npy` (init time, C, lead time); `--spectrum_lat_band LO HI` keeps the rows between two latitudes.
+`--event CHANNEL gt|lt VALUE` (any number of times; `--event_anomaly` the same on the value minus the climatology) verifies threshold
+events (`ldc_rollout_events`, not in the reference): the histogram of "members showing the event" against "the truth showed it", pooled
+over the initial times (`event_hist.npy`, `event_hist_weighted.npy` (E, lead time, ens + 1, 2)), `event_n_invalid.npy` (init time, E, lead
+time), `events.json`, and from the pooled histogram `event_brier.npy`, `event_bss.npy`, `event_reliability.npy`, `event_resolution.npy`,
+`event_uncertainty.npy`, `event_roc_area.npy` (E, lead time).
 Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
 members and the reference's commented-out `single_mse` are out of scope.
 """
@@ -31,14 +36,16 @@ from typing import Callable, Dict, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from .track import VARIABLE_NAMES, mean_std_from_json
-from .utils import (SCORE_NAMES, SPECTRUM_NAMES, empty_reliability, empty_spectrum, get_normalized_lat_weights_based_on_cos, rollout_reliability,
-                    rollout_scores, rollout_spectrum)
+from .track import LEVELS, NUM_ATM_VARS, VARIABLE_NAMES, mean_std_from_json
+from .utils import (SCORE_NAMES, SPECTRUM_NAMES, Event, empty_events, empty_reliability, empty_spectrum, event_scores,
+                    get_normalized_lat_weights_based_on_cos, rollout_events, rollout_reliability, rollout_scores, rollout_spectrum)
 
 SST_CHANNEL_IDX = 82
 CLIMATOLOGY_HOURS = (0, 6, 12, 18)
 RELIABILITY_KEYS = ("ens_var", "ssr", "rank_hist", "rank_hist_weighted", "n_invalid")  # what `--reliability` adds
 SPECTRUM_KEYS = SPECTRUM_NAMES + ("spec_n_invalid",)  # what `--spectrum` adds
+EVENTS_KEYS = ("event_hist", "event_hist_weighted", "event_n_invalid")  # what `--event` / `--event_anomaly` add to one initial time
+EVENT_FILE_SCORES = ("brier", "bss", "reliability", "resolution", "uncertainty", "roc_area")  # event_<name>.npy, from the pooled histogram
 
 
 def _to_datetime(t) -> datetime:
@@ -97,7 +104,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                          clim, clim_slots: Optional[Sequence[int]], lat_weight: torch.Tensor, *, sst_channel: int = SST_CHANNEL_IDX,
                          total_num_steps: Optional[int] = None, crop_init: bool = False, force_ens_size: Optional[int] = None,
                          decode_batch_frames: Optional[int] = None, reliability: bool = False, spectrum: bool = False,
-                         spectrum_row_weight: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                         spectrum_row_weight: Optional[torch.Tensor] = None, events: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -116,7 +123,12 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     `spectrum`: every decode batch also goes through `ldc_rollout_spectrum` while it is on the device and the result gains
     `SPECTRUM_KEYS`: `spec_members`, `spec_mean`, `spec_truth` (C, total_num_steps, W / 2 + 1) fp32 and `spec_n_invalid` (C, total_num_steps)
     int32.  `spectrum_row_weight` (H,), non-negative, weights the rows (0: the row is left out and never read); default: `lat_weight`.  The
-    five scores and the reliability outputs are the bits of a call without it."""
+    five scores and the reliability outputs are the bits of a call without it.
+
+    `events`: a sequence of `Event(channel, "gt" | "lt", threshold, anomaly)`; every decode batch also goes through `ldc_rollout_events`
+    while it is on the device and the result gains `EVENTS_KEYS`: `event_hist` (E, total_num_steps, ens + 1, 2) int32, `event_hist_weighted`
+    the same in fp32 and `event_n_invalid` (E, total_num_steps) int32 (`rollout_events`).  An anomaly event with `clim` None is a
+    ValueError.  The five scores, the reliability outputs and the spectrum outputs are the bits of a call without it."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
 
@@ -138,6 +150,9 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
         raise ValueError(f"nothing to score in latents of shape {tuple(latents.shape)}")
     if len(truth_slots) < T or (clim is not None and len(clim_slots) < T):
         raise ValueError(f"{T} lead times need {T} truth and climatology slots")
+    events = [Event(*ev) for ev in events] if events else None
+    if events and clim is None and any(ev.anomaly for ev in events):
+        raise ValueError("an anomaly event needs the climatology (clim)")
     dev = encdec_model.device
     if torch.device(dev).type != "cuda":
         raise RuntimeError("ladcast_amd scoring needs the model on the device (no CPU fallback)")
@@ -155,7 +170,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             raise ValueError("spectrum_row_weight must be non-negative (0 leaves a row out) and not NaN")
         spec_w = spec_w.to(dev, torch.float32)
     per = max(1, int(decode_batch_frames) // ens) if decode_batch_frames else 1  # lead times per decoder call: a lead time's members stay together
-    scores = rel = spec = None
+    scores = rel = spec = evs = None
     for s0 in range(0, T, per):
         nl = min(per, T - s0)
         x = latents[:, :, s0 : s0 + nl].permute(2, 0, 1, 3, 4).reshape(nl * ens, C, h, w).contiguous()  # lead-major, then member
@@ -174,12 +189,20 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                 spec = empty_spectrum(y.shape[1], total, y.shape[3], dev)
             rollout_spectrum(y.reshape(nl, ens, *y.shape[1:]), truth, spec_w, lead_dim=0, mean=mean_d, std=std_d,
                              truth_slot=t_slots[s0 : s0 + nl], out=spec, l_off=s0)
+        if events:
+            if evs is None:
+                evs = empty_events(ens, len(events), total, dev)
+            rollout_events(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, events, clim=clim,
+                           clim_slots=None if clim is None else c_slots[s0 : s0 + nl], lead_dim=0, mean=mean_d, std=std_d,
+                           truth_slot=t_slots[s0 : s0 + nl], out=evs, l_off=s0)
     host = scores.cpu()  # the one copy (and the one wait) of this initial time
     res = {k: host[i] for i, k in enumerate(SCORE_NAMES)}
     if reliability:
         res.update({k: rel[k].cpu() for k in RELIABILITY_KEYS})
     if spectrum:
         res.update({k: spec[k].cpu() for k in SPECTRUM_NAMES}, spec_n_invalid=spec["n_invalid"].cpu())
+    if events:
+        res.update({k: evs[k].cpu() for k in EVENTS_KEYS})
     return res
 
 
@@ -255,6 +278,47 @@ def _gather_spectrum(spec: dict, res, time_str: str, total_num_steps: int) -> No
     spec["spec_n_invalid"].append(a["spec_n_invalid"].astype(np.int32))
 
 
+def _gather_events(evs: dict, res, time_str: str, total_num_steps: int, E: int) -> None:
+    """one initial time's `EVENTS_KEYS` into the run's: `event_n_invalid` (int32) is kept per initial time, the histograms are summed over
+    the initial times on the host - the counts in int64, the weighted ones in float64"""
+    missing = [k for k in EVENTS_KEYS if k not in res]
+    if missing:
+        raise ValueError(f"{time_str}: --event needs {missing} from the scorer")
+    a = {k: np.asarray(res[k]) for k in EVENTS_KEYS}
+    shape = a["event_hist"].shape
+    if len(shape) != 4 or shape[:2] != (E, total_num_steps) or shape[3] != 2 or a["event_hist_weighted"].shape != shape \
+            or a["event_n_invalid"].shape != (E, total_num_steps):
+        raise ValueError(f"{time_str}: event arrays of shapes { {k: v.shape for k, v in a.items()} }, expected ({E}, {total_num_steps}, "
+                         f"members + 1, 2) and ({E}, {total_num_steps})")
+    if evs["event_hist"] is None:
+        evs["event_hist"], evs["event_hist_weighted"] = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.float64)
+    elif evs["event_hist"].shape != shape:
+        raise ValueError(f"{time_str}: an event histogram of {shape[2] - 1} members after one of {evs['event_hist'].shape[2] - 1}")
+    evs["event_n_invalid"].append(a["event_n_invalid"].astype(np.int32))
+    evs["event_hist"] += a["event_hist"].astype(np.int64)
+    evs["event_hist_weighted"] += a["event_hist_weighted"].astype(np.float64)
+
+
+def parse_events(event: Sequence[Sequence[str]], event_anomaly: Sequence[Sequence[str]], names: Sequence[str]):
+    """`--event` / `--event_anomaly CHANNEL gt|lt VALUE` entries -> (the `Event` list, plain events first; the entries as they go into
+    events.json, with the resolved channel names)"""
+    from .products import DIRECTIONS, resolve_channels
+
+    events, meta = [], []
+    for entries, anomaly in ((event, False), (event_anomaly, True)):
+        for chan, direction, value in entries:
+            flag = "--event_anomaly" if anomaly else "--event"
+            c = resolve_channels([chan], names)[0]
+            if direction not in DIRECTIONS:
+                raise ValueError(f"{flag} {chan} {direction}: the direction is gt or lt")
+            thr = float(value)
+            if thr != thr:
+                raise ValueError(f"{flag} {chan} {direction} {value}: the threshold must not be NaN")
+            events.append(Event(c, direction, thr, anomaly))
+            meta.append(dict(channel=names[c], channel_index=c, direction=direction, threshold=thr, anomaly=anomaly))
+    return events, meta
+
+
 def spectrum_band_weights(lat_weight: torch.Tensor, lat_deg, band) -> torch.Tensor:
     """`lat_weight` (H,) with the rows whose latitude `lat_deg` (H,) lies outside [band[0], band[1]] degrees set to 0; band None: unchanged"""
     if band is None:
@@ -287,6 +351,13 @@ def main(argv=None, score: Optional[Callable] = None):
     lead time, W / 2 + 1) fp32 and `spec_n_invalid.npy` (init time, C, lead time) int32; `--spectrum_lat_band LO HI` (degrees) gives the
     rows outside the band weight 0, the rows inside keep the cos weight.
 
+    `--event CHANNEL gt|lt VALUE` and `--event_anomaly CHANNEL gt|lt VALUE` (each any number of times; CHANNEL a name of
+    `products.column_names` or an index; the scorer then returns `EVENTS_KEYS` too, plain events first) add `event_hist.npy` (E, lead time,
+    members + 1, 2) int64 and `event_hist_weighted.npy` float64, summed over the initial times, `event_n_invalid.npy` (init time, E, lead
+    time) int32, `events.json` (the events as given, with resolved channel names) and `event_brier.npy`, `event_bss.npy`,
+    `event_reliability.npy`, `event_resolution.npy`, `event_uncertainty.npy`, `event_roc_area.npy` (E, lead time) float64: `event_scores`
+    of the pooled weighted histogram.  Without the flags the launches and the files are those of a run before they existed.
+
     `timestamp.npy` is float32, as the reference stores it: YYYYMMDDHH does not fit fp32's 24 bits, e.g. 2018123118 reads back as
     2018123136.  The per-time file names carry the exact time."""
     ap = argparse.ArgumentParser(description="Score saved ensemble rollouts (evaluate_ens_gpu.py on .npy data)")
@@ -312,6 +383,12 @@ def main(argv=None, score: Optional[Callable] = None):
     ap.add_argument("--spectrum", action="store_true", help="also write spec_members, spec_mean, spec_truth and spec_n_invalid")
     ap.add_argument("--spectrum_lat_band", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="latitudes in degrees between which rows enter the spectra (default: all rows)")
+    ap.add_argument("--event", nargs=3, action="append", default=[], metavar=("CHANNEL", "gt|lt", "VALUE"),
+                    help="verify the event 'CHANNEL above (gt) / below (lt) VALUE' (physical units); may be given several times")
+    ap.add_argument("--event_anomaly", nargs=3, action="append", default=[], metavar=("CHANNEL", "gt|lt", "VALUE"),
+                    help="the same on CHANNEL minus its climatology")
+    ap.add_argument("--levels", type=int, nargs="+", default=LEVELS, help="pressure levels of the atmospheric variables, in channel order (--event channel names)")
+    ap.add_argument("--num_atm_vars", type=int, default=NUM_ATM_VARS, help="leading variables that have one channel per level (--event channel names)")
     args = ap.parse_args(argv)
 
     if args.total_lead_time_hour % args.step_size_hour != 0:
@@ -325,6 +402,12 @@ def main(argv=None, score: Optional[Callable] = None):
     files = list_latent_files(args.result_path, end_date=args.end_date, total_lead_time_hour=args.total_lead_time_hour)
     if not files:
         raise SystemExit(f"{args.result_path}: no latent_*.npy at or before end_date - total_lead_time_hour")
+
+    events, events_meta = [], []
+    if args.event or args.event_anomaly:
+        from .validate_AR import column_names
+
+        events, events_meta = parse_events(args.event, args.event_anomaly, column_names(args.variable_names, args.levels, args.num_atm_vars))
 
     if score is None:
         if args.encdec_model is None or args.data_path is None or args.climatology_path is None:
@@ -351,12 +434,13 @@ def main(argv=None, score: Optional[Callable] = None):
             return score_latent_rollout(path, model, mean_t, std_t, truth, t_slots, clim, c_slots, lat_w, sst_channel=args.sst_channel_idx,
                                         total_num_steps=total_num_steps, crop_init=args.crop_init, force_ens_size=args.force_ens_size,
                                         decode_batch_frames=args.decode_batch_frames, reliability=args.reliability, spectrum=args.spectrum,
-                                        spectrum_row_weight=spec_w)
+                                        spectrum_row_weight=spec_w, events=events or None)
 
     os.makedirs(args.output, exist_ok=True)
     gathered = {k: [] for k in SCORE_NAMES}
     rel = dict(ens_var=[], ssr=[], n_invalid=[], rank_hist=None, rank_hist_weighted=None)
     spec = {k: [] for k in SPECTRUM_KEYS}
+    evs = dict(event_n_invalid=[], event_hist=None, event_hist_weighted=None)
     for i, (time_str, path) in enumerate(files):
         print(f"processing time_str: {time_str}, remaining: {len(files) - i - 1}")
         init = _to_datetime(int(time_str))
@@ -372,11 +456,19 @@ def main(argv=None, score: Optional[Callable] = None):
             _gather_reliability(rel, res, time_str, total_num_steps)
         if args.spectrum:
             _gather_spectrum(spec, res, time_str, total_num_steps)
+        if events:
+            _gather_events(evs, res, time_str, total_num_steps, len(events))
     out = {k: np.stack(v) for k, v in gathered.items()}
     if args.reliability:
         out.update({k: np.stack(rel[k]) for k in ("ens_var", "ssr", "n_invalid")}, rank_hist=rel["rank_hist"], rank_hist_weighted=rel["rank_hist_weighted"])
     if args.spectrum:
         out.update({k: np.stack(v) for k, v in spec.items()})
+    if events:
+        out.update(event_n_invalid=np.stack(evs["event_n_invalid"]), event_hist=evs["event_hist"], event_hist_weighted=evs["event_hist_weighted"])
+        sc = event_scores(evs["event_hist_weighted"])
+        out.update({f"event_{k}": np.asarray(sc[k], dtype=np.float64) for k in EVENT_FILE_SCORES})
+        with open(os.path.join(args.output, "events.json"), "w") as f:
+            json.dump(dict(events=events_meta), f, indent=1)
     out["timestamp"] = np.array([int(t) for t, _ in files]).astype(np.float32)  # as the reference: a float32 tensor of YYYYMMDDHH
     for k, a in out.items():
         np.save(os.path.join(args.output, f"{k}.npy"), a)

@@ -2,7 +2,7 @@
 ladcast/evaluate/evaluate_ens_gpu.py:339-425).  Same function names and argument meaning; the forecast is read once by
 one fused HIP kernel (`ldc_ensemble_scores`) instead of ~40 torch ops.  Tensors must live on a HIP device: there is no
 CPU path."""
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -483,3 +483,159 @@ def rollout_products(forecast: torch.Tensor, *, quantiles=(), thresholds=None, t
                          channels=chan_d, thr=thr_d, stats=st, quant=qu, exceed=ex, mean=mn, std=sd, target_std=target_std, L_total=L_total,
                          l_off=l_off)
     return ProductsDict(*bufs)
+
+
+MAX_EVENTS, MAX_EVENT_MEMBERS = hip.EVENTS_MAX, hip.EVENTS_MAX_MEMBERS
+EVENT_DIRECTIONS = {"gt": 1, "lt": -1}  # an event's direction as the command lines spell it (products.DIRECTIONS)
+
+
+class Event(NamedTuple):
+    """a threshold event of one channel: the value (`anomaly`: the value minus the climatology) lies above (`gt`) or below (`lt`) `threshold`"""
+
+    channel: int
+    direction: str
+    threshold: float
+    anomaly: bool = False
+
+
+class EventsDict(dict):
+    """{event_hist: (E, L_total, M + 1, 2) int32; event_hist_weighted: the same in fp32; event_n_invalid: (E, L_total) int32} over the
+    three device buffers `ldc_rollout_events` fills: entry [e, l, n, o] holds the points at which n members show event e and the truth
+    does (o = 1) or does not (o = 0)"""
+
+    def __init__(self, hist, hist_w, n_invalid):
+        super().__init__(event_hist=hist, event_hist_weighted=hist_w, event_n_invalid=n_invalid)
+        self._buffers = (hist, hist_w, n_invalid)
+
+
+def empty_events(M: int, E: int, L_total: int, device) -> EventsDict:
+    """the result of `rollout_events` before any column is written: empty histograms, `event_n_invalid` zero"""
+    return EventsDict(torch.zeros(E, L_total, M + 1, 2, device=device, dtype=torch.int32),
+                      torch.zeros(E, L_total, M + 1, 2, device=device, dtype=torch.float32),
+                      torch.zeros(E, L_total, device=device, dtype=torch.int32))
+
+
+def _event_list(events, C: int, has_clim: bool):
+    """`events` (Event, or (channel, direction, threshold[, anomaly]) tuples) -> the (channel, dir, thr, anomaly) rows of `hip.events_desc`;
+    every mistake is a ValueError"""
+    rows = []
+    for ev in events:
+        ev = Event(*ev)
+        if ev.direction not in EVENT_DIRECTIONS:
+            raise ValueError(f"event {tuple(ev)}: the direction is 'gt' or 'lt'")
+        c, thr = int(ev.channel), float(ev.threshold)
+        if not 0 <= c < C:
+            raise ValueError(f"event {tuple(ev)}: channel {c} is not one of the forecast's {C}")
+        if thr != thr:
+            raise ValueError(f"event {tuple(ev)}: the threshold must not be NaN")
+        if ev.anomaly and not has_clim:
+            raise ValueError(f"event {tuple(ev)}: an anomaly event needs the climatology (clim)")
+        rows.append((c, EVENT_DIRECTIONS[ev.direction], thr, 1 if ev.anomaly else 0))
+    if not 1 <= len(rows) <= MAX_EVENTS:
+        raise ValueError(f"{len(rows)} events: ldc_rollout_events takes 1 .. {MAX_EVENTS} per call")
+    return rows
+
+
+@torch.no_grad()
+def rollout_events(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torch.Tensor, events, *, clim: Optional[torch.Tensor] = None,
+                   clim_slots=None, lead_dim: int = 2, mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None,
+                   target_std: float = 1.0, truth_slot=None, out: Optional[Dict[str, torch.Tensor]] = None,
+                   l_off: int = 0) -> Dict[str, torch.Tensor]:
+    """The verification histogram of threshold events for every lead time in one launch (`ldc_rollout_events`; not in the reference).
+    Per grid point of event e = `Event(channel, "gt" | "lt", threshold, anomaly)`, with the members x_i of that channel, truth t and
+    climatology a: u_i = x_i and v = t, or with `anomaly` u_i = x_i - a and v = t - a (one fp32 subtraction each);
+        n = #{u_i > threshold} in 0 .. M,  o = (v > threshold) in {0, 1}      ("lt": < in place of >)
+    `event_hist[e, l, n, o]` counts the points, `event_hist_weighted` sums their latitude weights and `event_n_invalid[e, l]` counts the
+    points left out: those with a NaN member, a NaN truth or (anomaly events) a NaN climatology; +-inf are ordinary ordered values.
+    Histograms add over initial times; `event_scores` turns a (pooled) histogram into the Brier score and its decomposition, the
+    reliability curve and the ROC curve.  1 <= M <= 1024, at most 32 events; thresholds in physical units.
+
+    forecast, `lead_dim`, `mean` / `std` / `target_std`, truth / `truth_slot`, `out` / `l_off`: as `rollout_reliability`.  `clim` /
+    `clim_slots`: as `rollout_scores`; needed by anomaly events only.  Returns an `EventsDict` of device tensors with L_total = l_off + L
+    columns (unwritten columns: empty histograms), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or
+    `empty_events`) returned for the same ensemble size and number of events."""
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
+    if not 1 <= M <= MAX_EVENT_MEMBERS:
+        raise ValueError(f"{M} members: ldc_rollout_events serves 1 .. {MAX_EVENT_MEMBERS}")
+    dev = f.device
+    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
+    c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
+    w = _row_weight(lat_weight, H, dev, "lat_weight")
+    mn, sd = _channel_affine(mean, std, C, dev)
+    desc = hip.events_desc(_event_list(events, C, clim is not None))
+    E = desc.n_events
+    if l_off < 0:
+        raise ValueError("l_off must not be negative")
+    bufs = None
+    if out is not None:
+        bufs = getattr(out, "_buffers", None)
+        ok = bufs is not None and len(bufs) == 3 and bufs[0].dim() == 4 and all(b.is_contiguous() and b.device == dev for b in bufs)
+        if ok:
+            Lt = bufs[0].shape[1]
+            ok = l_off + L <= Lt and tuple(bufs[0].shape) == (E, Lt, M + 1, 2) and bufs[1].shape == bufs[0].shape and tuple(bufs[2].shape) == (E, Lt) \
+                and bufs[0].dtype == torch.int32 and bufs[1].dtype == torch.float32 and bufs[2].dtype == torch.int32
+        if not ok:
+            raise ValueError("out must be the dict an earlier rollout_events call (or empty_events) returned for the same ensemble size and "
+                             "number of events, with room for columns l_off .. l_off + L - 1")
+    hip._dev(forecast, truth, clim, lat_weight, mean, std)
+    if bufs is None:
+        bufs = empty_events(M, E, l_off + L, dev)._buffers
+    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], dev)
+    hip.rollout_events(f, t, slots[0], c, None if c is None else slots[1], w, desc, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0),
+                       lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs,
+                       clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mn, std=sd, target_std=target_std, L_total=bufs[0].shape[1],
+                       l_off=l_off)
+    return EventsDict(*bufs)
+
+
+EVENT_SCORE_NAMES = ("brier", "reliability", "resolution", "uncertainty", "bss", "base_rate", "forecast_mean", "roc_area")
+
+
+def event_scores(hist_weighted) -> Dict[str, "numpy.ndarray"]:  # noqa: F821
+    """Every score of a threshold event from its verification histogram, on the host in float64 (numpy; no device).
+
+    hist_weighted: (..., M + 1, 2) weights (or counts): entry [n, o] is the weight of the points at which n of the M members showed the
+    event and the truth did (o = 1) or did not (o = 0) - `event_hist_weighted` of `rollout_events`, pooled over any number of initial
+    times.  With p_n = n / M, W_n = W_n0 + W_n1, W = sum_n W_n, obar = sum_n W_n1 / W and o_n = W_n1 / W_n:
+        brier         sum_n [W_n0 p_n^2 + W_n1 (p_n - 1)^2] / W
+        reliability   sum_n W_n (p_n - o_n)^2 / W            resolution   sum_n W_n (o_n - obar)^2 / W
+        uncertainty   obar (1 - obar)                        brier = reliability - resolution + uncertainty, exactly: p takes M + 1 values
+        bss           1 - brier / uncertainty (NaN when the uncertainty is 0)
+        base_rate     obar                                   forecast_mean  sum_n W_n p_n / W
+        rel_prob, rel_obs, rel_weight   (..., M + 1): the reliability curve (p_n, o_n, W_n / W)
+        roc_pofd, roc_pod   (..., M + 2): "warn when n >= k" for k = M + 1 .. 0, from (0, 0) to (1, 1): pod_k = sum_{n >= k} W_n1 / sum_n W_n1,
+                      pofd_k = sum_{n >= k} W_n0 / sum_n W_n0
+        roc_area      the trapezoid rule over those points (NaN when one class is empty)
+    Empty bins contribute 0 to the sums and NaN to the curve; W == 0 gives NaN throughout.  Returns a dict of float64 arrays of shape
+    (...) (`EVENT_SCORE_NAMES`) and the curves."""
+    import numpy as np
+
+    h = np.asarray(hist_weighted, dtype=np.float64)
+    if h.ndim < 2 or h.shape[-1] != 2 or h.shape[-2] < 2:
+        raise ValueError(f"a verification histogram is (..., M + 1, 2) with M >= 1, got {h.shape}")
+    M = h.shape[-2] - 1
+    p = np.arange(M + 1, dtype=np.float64) / M
+    w0, w1 = h[..., 0], h[..., 1]
+    wn = w0 + w1
+    W, W1, W0 = wn.sum(-1), w1.sum(-1), w0.sum(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        obar = W1 / W
+        on = w1 / wn  # NaN in an empty bin
+        brier = (w0 * p ** 2 + w1 * (p - 1.0) ** 2).sum(-1) / W
+        filled = wn > 0
+        rel = np.where(filled, wn * (p - np.where(filled, on, 0.0)) ** 2, 0.0).sum(-1) / W
+        res = np.where(filled, wn * (np.where(filled, on, 0.0) - obar[..., None]) ** 2, 0.0).sum(-1) / W
+        unc = obar * (1.0 - obar)
+        bss = np.where(unc > 0, 1.0 - brier / np.where(unc > 0, unc, 1.0), np.nan)
+        bss = np.where(np.isnan(unc), np.nan, bss)
+        fmean = (wn * p).sum(-1) / W
+        rel_weight = wn / W[..., None]
+        # "warn when n >= k", k = M + 1 (never) .. 0 (always): cumulative sums from the top bin down, a leading zero for k = M + 1
+        zero = np.zeros(h.shape[:-2] + (1,))
+        hits = np.concatenate([zero, np.cumsum(w1[..., ::-1], -1)], -1)
+        fals = np.concatenate([zero, np.cumsum(w0[..., ::-1], -1)], -1)
+        pod, pofd = hits / hits[..., -1:], fals / fals[..., -1:]  # the totals as the cumulative sums end: the curve closes at exactly (1, 1)
+        area = (0.5 * (pod[..., 1:] + pod[..., :-1]) * (pofd[..., 1:] - pofd[..., :-1])).sum(-1)
+        area = np.where((W1 > 0) & (W0 > 0), area, np.nan)
+    return dict(brier=brier, reliability=rel, resolution=res, uncertainty=unc, bss=bss, base_rate=obar, forecast_mean=fmean, roc_area=area,
+                rel_prob=np.broadcast_to(p, on.shape).copy(), rel_obs=on, rel_weight=rel_weight, roc_pofd=pofd, roc_pod=pod)

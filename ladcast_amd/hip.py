@@ -61,6 +61,14 @@ class ProductsDesc(Structure):  # ldc_products_desc
                 ("thr_dir", c_int * PRODUCTS_MAX_THRESHOLDS)]
 
 
+EVENTS_MAX, EVENTS_MAX_MEMBERS = 32, 1024  # LDC_EVENTS_MAX, the largest ensemble of ldc_rollout_events
+
+
+class EventsDesc(Structure):  # ldc_events_desc
+    _fields_ = [("n_events", c_int), ("channel", c_int * EVENTS_MAX), ("dir", c_int * EVENTS_MAX), ("anomaly", c_int * EVENTS_MAX),
+                ("thr", c_float * EVENTS_MAX)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
@@ -122,6 +130,9 @@ def _load():
         "ldc_rollout_spectrum": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, P, P, I, I, P, L, P]),
         "ldc_sizeof_products_desc": (I, []),
         "ldc_rollout_products": (I, [P, L, L, L, P, P, F, P, I, I, I, I, I, I, POINTER(ProductsDesc), P, P, P, P, I, I, P]),
+        "ldc_sizeof_events_desc": (I, []),
+        "ldc_rollout_events_workspace_bytes": (L, [I, I, I, I, I]),
+        "ldc_rollout_events": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, POINTER(EventsDesc), P, P, P, I, I, P, L, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
         "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
         "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
@@ -178,6 +189,8 @@ def _load():
         raise RuntimeError("ldc_qkv_epilogue layout mismatch between header and binding")
     if lib.ldc_sizeof_products_desc() != ctypes.sizeof(ProductsDesc):
         raise RuntimeError("ldc_products_desc layout mismatch between header and binding")
+    if lib.ldc_sizeof_events_desc() != ctypes.sizeof(EventsDesc):
+        raise RuntimeError("ldc_events_desc layout mismatch between header and binding")
     return lib, sig
 
 
@@ -392,7 +405,7 @@ def ensemble_scores(forecast, truth, clim, lat_weight, out, *, M, C, H, W, membe
 
 
 def _forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std):
-    """the leading arguments of ldc_rollout_scores / _reliability / _spectrum / _products and ldc_validation_scores"""
+    """the leading arguments of ldc_rollout_scores / _reliability / _spectrum / _products / _events and ldc_validation_scores"""
     return _p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std)
 
 
@@ -485,6 +498,39 @@ def rollout_products(forecast, desc, *, M, C, L, H, W, member_stride, lead_strid
     _check(lib.ldc_rollout_products(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
                                     _p(channels), M, C, C if Cs is None else Cs, L, H, W, ctypes.byref(desc), _p(thr), _p(stats), _p(quant),
                                     _p(exceed), L_total, l_off, _stream()), "ldc_rollout_products")
+
+
+def events_desc(events):
+    """ldc_events_desc for a sequence of (channel, dir, thr, anomaly): dir +1 (value > thr) or -1 (value < thr), thr in physical units,
+    anomaly 1 (the value is x - climatology) or 0.  Host only; the channel range is checked by the caller, who knows C."""
+    ev = [(int(c), int(d), float(t), int(a)) for c, d, t, a in events]
+    if not 1 <= len(ev) <= EVENTS_MAX:
+        raise ValueError(f"{len(ev)} events: ldc_rollout_events takes 1 .. {EVENTS_MAX} per call")
+    if any(d not in (1, -1) for _, d, _, _ in ev):
+        raise ValueError(f"an event's direction is +1 (above) or -1 (below), got {[d for _, d, _, _ in ev]}")
+    if any(a not in (0, 1) for _, _, _, a in ev):
+        raise ValueError("an event's anomaly flag is 0 or 1")
+    if any(t != t for _, _, t, _ in ev):
+        raise ValueError("an event's threshold must not be NaN")
+    d = EventsDesc()
+    d.n_events = len(ev)
+    for k, (c, dr, t, a) in enumerate(ev):
+        d.channel[k], d.dir[k], d.thr[k], d.anomaly[k] = c, dr, t, a  # the threshold rounds to fp32
+    return d
+
+
+def rollout_events(forecast, truth, truth_slot, clim, clim_slot, lat_weight, desc, hist_count, hist_weight, n_invalid, *, M, C, L, H, W,
+                   member_stride, lead_stride, channel_stride, truth_slot_stride, truth_channel_stride, clim_slot_stride=0,
+                   clim_channel_stride=0, mean=None, std=None, target_std=1.0, L_total, l_off=0):
+    """hist_count (int32) / hist_weight [E][L_total][M + 1][2]; n_invalid (int32) [E][L_total]: columns l_off .. l_off + L - 1 of L lead
+    times in one launch (ladcast_hip.h: ldc_rollout_events); desc: `events_desc`; truth_slot / clim_slot: device int32 [L]"""
+    _dev(forecast, truth, truth_slot, clim, clim_slot, lat_weight, hist_count, hist_weight, n_invalid, mean, std)
+    nbytes = int(lib.ldc_rollout_events_workspace_bytes(M, desc.n_events, L, H, W))
+    ws = _workspace("rollout_events", forecast.device, max(nbytes, 4), grow=True)
+    _check(lib.ldc_rollout_events(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                  *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
+                                  clim_channel_stride, _p(clim_slot), _p(lat_weight), M, C, L, H, W, ctypes.byref(desc), _p(hist_count),
+                                  _p(hist_weight), _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_events")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):
