@@ -705,6 +705,41 @@ int ldc_rollout_events(const float* forecast, long long member_stride, long long
                        long long clim_channel_stride, const int* clim_slot, const float* lat_weight, int M, int C, int L, int H, int W,
                        const ldc_events_desc* desc, int* hist_count, float* hist_weight, int* n_invalid, int L_total, int l_off,
                        void* workspace, long long workspace_bytes, void* stream);
+/* Regional ensemble scores for every lead time of a decode batch in one launch (additive under ABI 5; regional.hip, DESIGN.md section
+ * 8.5): for up to 32 regions that may overlap, the additive sufficient statistics of bias, RMSE, spread, spread-skill ratio, CRPS and
+ * ACC per (region, channel, lead time).  ladcast_amd.evaluate.regional_scores derives the scores on the host in float64; sums of several
+ * initial times add.  Not in the reference.  Addressing of forecast, inverse normalisation (mean == NULL: physical units), truth and
+ * climatology tables (clim == NULL: no ACC terms), lat_weight and output columns exactly as ldc_rollout_scores.  1 <= M <= 64.
+ * region_mask: DEVICE uint32 [H * W]; bit r of word p says that point p belongs to region r, r < R <= 32 (bits >= R are ignored).
+ *   Regions may overlap, be empty, or leave points uncovered.  A point with no bit below R is not read: NaN or inf there has no effect.
+ * Per point, all fp32, the members x_i in member order after the inverse normalisation, truth t, weight w = lat_weight[row],
+ * climatology a, each value formed as the kernel that already has it forms it:
+ *   mean = (x_0 + ... + x_{M-1}) / M (sequential), e = mean - t, se = e * e                    (ldc_rollout_scores)
+ *   var = sum_i (x_i - mean)^2 / (M - 1), two-pass in member order; M == 1: 0                  (ldc_rollout_reliability)
+ *   skill = sum_i |t - x_i| / M;  spread = 2 / (M (M - 1)) * sum_i (2 i - M - 1) x_(i) over the sorted members; M == 1: 0
+ *   fa = mean - a, ta = t - a, and the fp32 products fa * ta, fa * fa, ta * ta
+ * Validity: a point is valid when no member and not the truth is NaN, ACC-valid when it is valid and a is not NaN; +-inf are ordinary
+ *   values (the sums then follow IEEE).  Unlike ldc_rollout_scores there is no mean / nanmean distinction and no nan_channel: in EVERY
+ *   channel the invalid points are left out and counted, so SST over land drops out by itself and one bad point does not make a
+ *   regional score NaN.
+ *   sums   [R][C][L_total][10] fp64: over the region's valid points  sum w, sum w e, sum w se, sum w var, sum w skill, sum w spread;
+ *     over its ACC-valid points  sum w, sum w fa ta, sum w fa^2, sum w ta^2 (these four are zeros when clim == NULL).  Every term is
+ *     double(w) * double(v), which is exact: the only rounding behind the fp32 point values is that of the fp64 additions.
+ *   counts [R][C][L_total][3] int32: the valid points of the region, the invalid ones, the ACC-valid ones.
+ *   Columns l_off .. l_off + L - 1 of both outputs are written, the others left alone.  No atomics: run-to-run bit-equal, and the sums
+ *   of region r do not depend on R or on the other regions (one region passed alone gives the bits it gives among 31 others).
+ * workspace: ldc_rollout_regional_workspace_bytes(M, R, C, L, H, W) bytes of device scratch, 8-byte aligned (0 for arguments the call
+ *   refuses): 1.5 bytes per point and (channel, lead time), whatever R is.
+ * LDC_ERR_ARG: a null or non-positive argument (R <= 0 among them), clim without clim_slot, mean without std_, l_off + L > L_total or a
+ * workspace that is too small; LDC_ERR_UNSUPPORTED: M > 64, R > 32, C > 65535, L > 65535 or H * W > 2^24; LDC_ERR_ALIGN: workspace or
+ * sums not 8-byte aligned.  Nothing is launched on an error. */
+long long ldc_rollout_regional_workspace_bytes(int M, int R, int C, int L, int H, int W);
+int ldc_rollout_regional(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride, const float* mean,
+                         const float* std_, float target_std, const float* truth, long long truth_slot_stride,
+                         long long truth_channel_stride, const int* truth_slot, const float* clim, long long clim_slot_stride,
+                         long long clim_channel_stride, const int* clim_slot, const float* lat_weight, const unsigned* region_mask, int R,
+                         int M, int C, int L, int H, int W, double* sums, int* counts, int L_total, int l_off, void* workspace,
+                         long long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

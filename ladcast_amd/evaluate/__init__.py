@@ -1,6 +1,7 @@
 from .utils import (EVENT_SCORE_NAMES, VALIDATION_SCORE_NAMES, Event, empty_events, empty_products, event_scores, rollout_events, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
                     get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_products, rollout_reliability, rollout_scores, rollout_spectrum,
                     validation_scores)
+from .regional import NAMED_REGIONS, REGIONAL_SCORE_NAMES, Region, empty_regional, region_mask, regional_scores, rollout_regional
 
 _DRIVER_NAMES = ("climatology_slots", "score_latent_rollout", "truth_frame_slots")  # evaluate_ens_gpu's, resolved at first use: the
 _VALIDATE_NAMES = ("NpyLatentStore", "log_validation", "validate_initial_time")  # validate_AR's, likewise
@@ -8,7 +9,8 @@ _DENOISE_NAMES = ("denoising_loss", "evaluate_denoising_loss", "push_forward_pla
 _PRODUCTS_NAMES = ("products_of_latent_rollout",)  # products', likewise
 __all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
            "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores", "rollout_spectrum",  # also runs
-           "validation_scores", "empty_products", "rollout_products", "EVENT_SCORE_NAMES", "Event", "empty_events", "event_scores", "rollout_events", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES]  # as `python -m`
+           "validation_scores", "empty_products", "rollout_products", "EVENT_SCORE_NAMES", "Event", "empty_events", "event_scores", "rollout_events", "NAMED_REGIONS", "REGIONAL_SCORE_NAMES",
+           "Region", "empty_regional", "region_mask", "regional_scores", "rollout_regional", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES]  # as `python -m`
 
 
 def __getattr__(name):

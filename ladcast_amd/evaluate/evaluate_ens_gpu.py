@@ -21,6 +21,11 @@ events (`ldc_rollout_events`, not in the reference): the histogram of "members s
 over the initial times (`event_hist.npy`, `event_hist_weighted.npy` (E, lead time, ens + 1, 2)), `event_n_invalid.npy` (init time, E, lead
 time), `events.json`, and from the pooled histogram `event_brier.npy`, `event_bss.npy`, `event_reliability.npy`, `event_resolution.npy`,
 `event_uncertainty.npy`, `event_roc_area.npy` (E, lead time).
+`--region NAME` (any number of times, from `NAMED_REGIONS`), `--region_box NAME LAT0 LAT1 LON0 LON1`, `--region_surface NAME land|sea`
+(with `--land_sea_mask_path`) break the scores down by region (`ldc_rollout_regional`, not in the reference): every region in one pass
+per decode batch, the additive sums pooled over the initial times (`regional_sums.npy` (R, C, lead time, 10), `regional_counts.npy`),
+`regional_bias.npy`, `regional_rmse.npy`, `regional_crps.npy`, ... (R, C, lead time) derived from the pooled sums, and `regions.json`;
+`--region_per_init` keeps the sums of every initial time too.
 Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
 members and the reference's commented-out `single_mse` are out of scope.
 """
@@ -37,6 +42,8 @@ import numpy as np
 import torch
 
 from .track import LEVELS, NUM_ATM_VARS, VARIABLE_NAMES, mean_std_from_json
+from .regional import (COUNT_NAMES, SUM_NAMES, REGIONAL_KEYS, REGIONAL_SCORE_NAMES, NAMED_REGIONS, Region, empty_regional, mask_words, region_mask as make_region_mask,
+                       region_metadata, regional_scores, rollout_regional)
 from .utils import (SCORE_NAMES, SPECTRUM_NAMES, Event, empty_events, empty_reliability, empty_spectrum, event_scores,
                     get_normalized_lat_weights_based_on_cos, rollout_events, rollout_reliability, rollout_scores, rollout_spectrum)
 
@@ -104,7 +111,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                          clim, clim_slots: Optional[Sequence[int]], lat_weight: torch.Tensor, *, sst_channel: int = SST_CHANNEL_IDX,
                          total_num_steps: Optional[int] = None, crop_init: bool = False, force_ens_size: Optional[int] = None,
                          decode_batch_frames: Optional[int] = None, reliability: bool = False, spectrum: bool = False,
-                         spectrum_row_weight: Optional[torch.Tensor] = None, events: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
+                         spectrum_row_weight: Optional[torch.Tensor] = None, events: Optional[Sequence] = None,
+                         regions: Optional[Sequence] = None, region_mask=None) -> Dict[str, torch.Tensor]:
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -128,7 +136,13 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     `events`: a sequence of `Event(channel, "gt" | "lt", threshold, anomaly)`; every decode batch also goes through `ldc_rollout_events`
     while it is on the device and the result gains `EVENTS_KEYS`: `event_hist` (E, total_num_steps, ens + 1, 2) int32, `event_hist_weighted`
     the same in fp32 and `event_n_invalid` (E, total_num_steps) int32 (`rollout_events`).  An anomaly event with `clim` None is a
-    ValueError.  The five scores, the reliability outputs and the spectrum outputs are the bits of a call without it."""
+    ValueError.  The five scores, the reliability outputs and the spectrum outputs are the bits of a call without it.
+
+    `regions`: a sequence of `Region` (or an int: their number), with `region_mask` the (H, W) uint32 mask of which bit r marks region
+    r (`regional.region_mask`; default: built from `regions` on `row_latitudes(H)` and the longitudes 0, 360 / W, ...); every decode
+    batch also goes through one `ldc_rollout_regional` launch while it is on the device and the result gains `REGIONAL_KEYS`:
+    `regional_sums` (R, C, total_num_steps, 10) float64 and `regional_counts` (R, C, total_num_steps, 3) int32 (`rollout_regional`;
+    columns past the last lead time are zeros).  Every other output is the bits of a call without it."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
 
@@ -153,6 +167,15 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     events = [Event(*ev) for ev in events] if events else None
     if events and clim is None and any(ev.anomaly for ev in events):
         raise ValueError("an anomaly event needs the climatology (clim)")
+    n_regions = 0
+    if regions is not None or region_mask is not None:
+        if regions is None:
+            raise ValueError("region_mask needs regions (the Region list, or their number)")
+        n_regions = int(regions) if isinstance(regions, (int, np.integer)) else len(regions)
+        if not 1 <= n_regions <= 32:
+            raise ValueError(f"{n_regions} regions: ldc_rollout_regional takes 1 .. 32 per call")
+        if region_mask is None and isinstance(regions, (int, np.integer)):
+            raise ValueError("a number of regions needs the region_mask")
     dev = encdec_model.device
     if torch.device(dev).type != "cuda":
         raise RuntimeError("ladcast_amd scoring needs the model on the device (no CPU fallback)")
@@ -170,7 +193,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             raise ValueError("spectrum_row_weight must be non-negative (0 leaves a row out) and not NaN")
         spec_w = spec_w.to(dev, torch.float32)
     per = max(1, int(decode_batch_frames) // ens) if decode_batch_frames else 1  # lead times per decoder call: a lead time's members stay together
-    scores = rel = spec = evs = None
+    scores = rel = spec = evs = reg = reg_words = None
     for s0 in range(0, T, per):
         nl = min(per, T - s0)
         x = latents[:, :, s0 : s0 + nl].permute(2, 0, 1, 3, 4).reshape(nl * ens, C, h, w).contiguous()  # lead-major, then member
@@ -195,6 +218,16 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             rollout_events(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, events, clim=clim,
                            clim_slots=None if clim is None else c_slots[s0 : s0 + nl], lead_dim=0, mean=mean_d, std=std_d,
                            truth_slot=t_slots[s0 : s0 + nl], out=evs, l_off=s0)
+        if n_regions:
+            if reg is None:
+                Hd, Wd = y.shape[2], y.shape[3]
+                if region_mask is None:
+                    region_mask = make_region_mask(regions, row_latitudes(Hd), np.arange(Wd) * (360.0 / Wd))
+                reg_words = region_mask if isinstance(region_mask, torch.Tensor) and region_mask.is_cuda else mask_words(region_mask, Hd, Wd).to(dev)
+                reg = empty_regional(n_regions, y.shape[1], total, dev)
+            rollout_regional(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, reg_words, n_regions, clim=clim,
+                             clim_slots=None if clim is None else c_slots[s0 : s0 + nl], lead_dim=0, mean=mean_d, std=std_d,
+                             truth_slot=t_slots[s0 : s0 + nl], out=reg, l_off=s0)
     host = scores.cpu()  # the one copy (and the one wait) of this initial time
     res = {k: host[i] for i, k in enumerate(SCORE_NAMES)}
     if reliability:
@@ -203,6 +236,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
         res.update({k: spec[k].cpu() for k in SPECTRUM_NAMES}, spec_n_invalid=spec["n_invalid"].cpu())
     if events:
         res.update({k: evs[k].cpu() for k in EVENTS_KEYS})
+    if n_regions:
+        res.update({k: reg[k].cpu() for k in REGIONAL_KEYS})
     return res
 
 
@@ -299,6 +334,56 @@ def _gather_events(evs: dict, res, time_str: str, total_num_steps: int, E: int) 
     evs["event_hist_weighted"] += a["event_hist_weighted"].astype(np.float64)
 
 
+def _gather_regional(regs: dict, res, time_str: str, total_num_steps: int, R: int, per_init: bool) -> None:
+    """one initial time's `REGIONAL_KEYS` into the run's: summed over the initial times on the host, the sums in float64 and the counts in
+    int64; `per_init` also keeps each initial time's sums"""
+    missing = [k for k in REGIONAL_KEYS if k not in res]
+    if missing:
+        raise ValueError(f"{time_str}: --region needs {missing} from the scorer")
+    s, n = np.asarray(res["regional_sums"], dtype=np.float64), np.asarray(res["regional_counts"]).astype(np.int64)
+    if s.ndim != 4 or s.shape[0] != R or s.shape[2:] != (total_num_steps, 10) or n.shape != s.shape[:3] + (3,):
+        raise ValueError(f"{time_str}: regional arrays of shapes {s.shape} and {n.shape}, expected ({R}, C, {total_num_steps}, 10) and "
+                         f"({R}, C, {total_num_steps}, 3)")
+    if regs["regional_sums"] is None:
+        regs["regional_sums"], regs["regional_counts"] = np.zeros(s.shape, dtype=np.float64), np.zeros(n.shape, dtype=np.int64)
+    elif regs["regional_sums"].shape != s.shape:
+        raise ValueError(f"{time_str}: regional sums of shape {s.shape} after {regs['regional_sums'].shape}")
+    regs["regional_sums"] += s
+    regs["regional_counts"] += n
+    if per_init:
+        regs["per_init"].append(s)
+
+
+def parse_regions(region: Sequence[str], region_box: Sequence[Sequence[str]], region_surface: Sequence[Sequence[str]]) -> List[Region]:
+    """`--region NAME`, `--region_box NAME LAT0 LAT1 LON0 LON1` and `--region_surface NAME land|sea` entries -> the `Region` list, named
+    regions first; a surface applies to the region of that name"""
+    regions: List[Region] = []
+    for name in region:
+        if name not in NAMED_REGIONS:
+            raise ValueError(f"--region {name}: not one of {sorted(NAMED_REGIONS)}")
+        regions.append(NAMED_REGIONS[name])
+    for name, *box in region_box:
+        try:
+            lat0, lat1, lon0, lon1 = (float(v) for v in box)
+        except ValueError:
+            raise ValueError(f"--region_box {name} {' '.join(box)}: four numbers are needed") from None
+        if not all(np.isfinite([lat0, lat1, lon0, lon1])) or lat0 > lat1:
+            raise ValueError(f"--region_box {name} {' '.join(box)}: finite bounds with LAT0 <= LAT1 are needed")
+        regions.append(Region(name, lat0, lat1, lon0, lon1))
+    names = [r.name for r in regions]
+    if len(set(names)) != len(names):
+        raise ValueError(f"region names must differ, got {names}")
+    for name, surface in region_surface:
+        if surface not in ("land", "sea"):
+            raise ValueError(f"--region_surface {name} {surface}: the surface is land or sea")
+        if name not in names:
+            raise ValueError(f"--region_surface {name}: no such region among {names}")
+        regions[names.index(name)] = regions[names.index(name)]._replace(surface=surface)
+    if len(regions) > 32:
+        raise ValueError(f"{len(regions)} regions: at most 32 per run")
+    return regions
+
+
 def parse_events(event: Sequence[Sequence[str]], event_anomaly: Sequence[Sequence[str]], names: Sequence[str]):
     """`--event` / `--event_anomaly CHANNEL gt|lt VALUE` entries -> (the `Event` list, plain events first; the entries as they go into
     events.json, with the resolved channel names)"""
@@ -358,6 +443,14 @@ def main(argv=None, score: Optional[Callable] = None):
     `event_reliability.npy`, `event_resolution.npy`, `event_uncertainty.npy`, `event_roc_area.npy` (E, lead time) float64: `event_scores`
     of the pooled weighted histogram.  Without the flags the launches and the files are those of a run before they existed.
 
+    `--region NAME` (from `NAMED_REGIONS`), `--region_box NAME LAT0 LAT1 LON0 LON1` (each any number of times; named regions first) and
+    `--region_surface NAME land|sea` with `--land_sea_mask_path` (.npy (H_in, W), land where >= 0.5; rows cropped as the truth's) make
+    the scorer return `REGIONAL_KEYS` too.  The sums are pooled over the initial times on the host (float64, counts in int64):
+    `regional_sums.npy` (R, C, lead time, 10), `regional_counts.npy` (R, C, lead time, 3), `regional_<score>.npy` (R, C, lead time) for
+    `REGIONAL_SCORE_NAMES` from the pooled sums (`regional_scores`) and `regions.json` (names, boxes, surface, point count and weight of
+    each region).  `--region_per_init` also writes `regional_sums_per_init.npy` (init time, R, C, lead time, 10): off by default, at a
+    year of initial times, 84 channels and 13 regions it runs to gigabytes.  Without the flags the launches and files are unchanged.
+
     `timestamp.npy` is float32, as the reference stores it: YYYYMMDDHH does not fit fp32's 24 bits, e.g. 2018123118 reads back as
     2018123136.  The per-time file names carry the exact time."""
     ap = argparse.ArgumentParser(description="Score saved ensemble rollouts (evaluate_ens_gpu.py on .npy data)")
@@ -387,6 +480,13 @@ def main(argv=None, score: Optional[Callable] = None):
                     help="verify the event 'CHANNEL above (gt) / below (lt) VALUE' (physical units); may be given several times")
     ap.add_argument("--event_anomaly", nargs=3, action="append", default=[], metavar=("CHANNEL", "gt|lt", "VALUE"),
                     help="the same on CHANNEL minus its climatology")
+    ap.add_argument("--region", action="append", default=[], metavar="NAME", help="break the scores down by this named region; may be given several times")
+    ap.add_argument("--region_box", nargs=5, action="append", default=[], metavar=("NAME", "LAT0", "LAT1", "LON0", "LON1"),
+                    help="a region of your own: latitudes LAT0 .. LAT1 (inclusive), longitudes LON0 .. LON1 east (LON0 > LON1: across 0 degrees)")
+    ap.add_argument("--region_surface", nargs=2, action="append", default=[], metavar=("NAME", "land|sea"),
+                    help="restrict the region NAME to land or sea points (needs --land_sea_mask_path)")
+    ap.add_argument("--land_sea_mask_path", type=str, default=None, help=".npy (H_in, W): land where >= 0.5")
+    ap.add_argument("--region_per_init", action="store_true", help="also write regional_sums_per_init.npy (init time, R, C, lead time, 10)")
     ap.add_argument("--levels", type=int, nargs="+", default=LEVELS, help="pressure levels of the atmospheric variables, in channel order (--event channel names)")
     ap.add_argument("--num_atm_vars", type=int, default=NUM_ATM_VARS, help="leading variables that have one channel per level (--event channel names)")
     args = ap.parse_args(argv)
@@ -409,6 +509,23 @@ def main(argv=None, score: Optional[Callable] = None):
 
         events, events_meta = parse_events(args.event, args.event_anomaly, column_names(args.variable_names, args.levels, args.num_atm_vars))
 
+    regions = parse_regions(args.region, args.region_box, args.region_surface)
+    if any(r.surface for r in regions) and args.land_sea_mask_path is None:
+        raise ValueError("--region_surface needs --land_sea_mask_path")
+    if not regions and (args.region_per_init or args.land_sea_mask_path or args.region_surface):
+        raise ValueError("--region_per_init, --region_surface and --land_sea_mask_path need --region or --region_box")
+    regions_meta = None
+
+    def build_region_mask(H: int, W: int, lat_w):
+        lsm = None
+        if args.land_sea_mask_path is not None:
+            lsm = np.load(args.land_sea_mask_path)
+            if lsm.ndim != 2:
+                raise ValueError(f"--land_sea_mask_path must be (H_in, W), got {lsm.shape}")
+            lsm = _crop_rows(lsm, H, "--land_sea_mask_path")
+        mask = make_region_mask(regions, row_latitudes(H), np.arange(W) * (360.0 / W), lsm)
+        return mask, region_metadata(regions, mask, lat_w)
+
     if score is None:
         if args.encdec_model is None or args.data_path is None or args.climatology_path is None:
             raise SystemExit("--encdec_model, --data_path and --climatology_path are required")
@@ -429,18 +546,22 @@ def main(argv=None, score: Optional[Callable] = None):
             clim = torch.from_numpy(np.ascontiguousarray(clim, dtype=np.float32)).to("cuda")
         lat_w = lat_weights_for(H)
         spec_w = spectrum_band_weights(lat_w, row_latitudes(H), args.spectrum_lat_band) if args.spectrum else None
+        reg_mask = None
+        if regions:
+            reg_mask, regions_meta = build_region_mask(H, truth.shape[-1], lat_w.numpy())
 
         def score(path, time_str, t_slots, c_slots):
             return score_latent_rollout(path, model, mean_t, std_t, truth, t_slots, clim, c_slots, lat_w, sst_channel=args.sst_channel_idx,
                                         total_num_steps=total_num_steps, crop_init=args.crop_init, force_ens_size=args.force_ens_size,
                                         decode_batch_frames=args.decode_batch_frames, reliability=args.reliability, spectrum=args.spectrum,
-                                        spectrum_row_weight=spec_w, events=events or None)
+                                        spectrum_row_weight=spec_w, events=events or None, regions=regions or None, region_mask=reg_mask)
 
     os.makedirs(args.output, exist_ok=True)
     gathered = {k: [] for k in SCORE_NAMES}
     rel = dict(ens_var=[], ssr=[], n_invalid=[], rank_hist=None, rank_hist_weighted=None)
     spec = {k: [] for k in SPECTRUM_KEYS}
     evs = dict(event_n_invalid=[], event_hist=None, event_hist_weighted=None)
+    regs = dict(regional_sums=None, regional_counts=None, per_init=[])
     for i, (time_str, path) in enumerate(files):
         print(f"processing time_str: {time_str}, remaining: {len(files) - i - 1}")
         init = _to_datetime(int(time_str))
@@ -458,6 +579,8 @@ def main(argv=None, score: Optional[Callable] = None):
             _gather_spectrum(spec, res, time_str, total_num_steps)
         if events:
             _gather_events(evs, res, time_str, total_num_steps, len(events))
+        if regions:
+            _gather_regional(regs, res, time_str, total_num_steps, len(regions), args.region_per_init)
     out = {k: np.stack(v) for k, v in gathered.items()}
     if args.reliability:
         out.update({k: np.stack(rel[k]) for k in ("ens_var", "ssr", "n_invalid")}, rank_hist=rel["rank_hist"], rank_hist_weighted=rel["rank_hist_weighted"])
@@ -469,6 +592,19 @@ def main(argv=None, score: Optional[Callable] = None):
         out.update({f"event_{k}": np.asarray(sc[k], dtype=np.float64) for k in EVENT_FILE_SCORES})
         with open(os.path.join(args.output, "events.json"), "w") as f:
             json.dump(dict(events=events_meta), f, indent=1)
+    if regions:
+        out.update(regional_sums=regs["regional_sums"], regional_counts=regs["regional_counts"])
+        ens = int(np.load(files[0][1], mmap_mode="r").shape[0])  # the members the sums were taken over: the ssr's (M + 1) / M
+        ens = ens if args.force_ens_size is None else min(ens, args.force_ens_size)
+        sc = regional_scores(regs["regional_sums"], regs["regional_counts"], ens)
+        out.update({f"regional_{k}": np.asarray(sc[k]) for k in REGIONAL_SCORE_NAMES})
+        if args.region_per_init:
+            out["regional_sums_per_init"] = np.stack(regs["per_init"])
+        if regions_meta is None:  # an injected scorer: the mask of the pooled arrays' grid is not known here
+            regions_meta = [dict(name=r.name, boxes=[[r.lat_min, r.lat_max, r.lon_min, r.lon_max]] + [list(b) for b in r.boxes], surface=r.surface,
+                                 n_points=None, weight=None) for r in regions]
+        with open(os.path.join(args.output, "regions.json"), "w") as f:
+            json.dump(dict(regions=regions_meta, members=ens, sums=list(SUM_NAMES), counts=list(COUNT_NAMES)), f, indent=1)
     out["timestamp"] = np.array([int(t) for t, _ in files]).astype(np.float32)  # as the reference: a float32 tensor of YYYYMMDDHH
     for k, a in out.items():
         np.save(os.path.join(args.output, f"{k}.npy"), a)

@@ -133,6 +133,8 @@ def _load():
         "ldc_sizeof_events_desc": (I, []),
         "ldc_rollout_events_workspace_bytes": (L, [I, I, I, I, I]),
         "ldc_rollout_events": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, POINTER(EventsDesc), P, P, P, I, I, P, L, P]),
+        "ldc_rollout_regional_workspace_bytes": (L, [I, I, I, I, I, I]),
+        "ldc_rollout_regional": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, P, I, I, I, I, I, I, P, P, I, I, P, L, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
         "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
         "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
@@ -405,7 +407,7 @@ def ensemble_scores(forecast, truth, clim, lat_weight, out, *, M, C, H, W, membe
 
 
 def _forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std):
-    """the leading arguments of ldc_rollout_scores / _reliability / _spectrum / _products / _events and ldc_validation_scores"""
+    """the leading arguments of ldc_rollout_scores / _reliability / _spectrum / _products / _events / _regional and ldc_validation_scores"""
     return _p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std)
 
 
@@ -531,6 +533,24 @@ def rollout_events(forecast, truth, truth_slot, clim, clim_slot, lat_weight, des
                                   *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
                                   clim_channel_stride, _p(clim_slot), _p(lat_weight), M, C, L, H, W, ctypes.byref(desc), _p(hist_count),
                                   _p(hist_weight), _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_events")
+
+
+REGIONS_MAX, REGIONAL_MAX_MEMBERS, REGIONAL_SUMS, REGIONAL_COUNTS = 32, 64, 10, 3  # the limits and the record of ldc_rollout_regional
+
+
+def rollout_regional(forecast, truth, truth_slot, clim, clim_slot, lat_weight, region_mask, sums, counts, *, R, M, C, L, H, W, member_stride,
+                     lead_stride, channel_stride, truth_slot_stride, truth_channel_stride, clim_slot_stride=0, clim_channel_stride=0,
+                     mean=None, std=None, target_std=1.0, L_total, l_off=0):
+    """sums (fp64) [R][C][L_total][10]; counts (int32) [R][C][L_total][3]: columns l_off .. l_off + L - 1 of L lead times in one launch
+    (ladcast_hip.h: ldc_rollout_regional); region_mask: device int32 / uint32 words [H * W], bit r = region r; truth_slot / clim_slot:
+    device int32 [L]"""
+    _dev(forecast, truth, truth_slot, clim, clim_slot, lat_weight, region_mask, sums, counts, mean, std)
+    nbytes = int(lib.ldc_rollout_regional_workspace_bytes(M, R, C, L, H, W))
+    ws = _workspace("rollout_regional", forecast.device, max(nbytes, 4), grow=True)
+    _check(lib.ldc_rollout_regional(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                    *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
+                                    clim_channel_stride, _p(clim_slot), _p(lat_weight), _p(region_mask), R, M, C, L, H, W, _p(sums), _p(counts),
+                                    L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_regional")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):
