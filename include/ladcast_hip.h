@@ -207,6 +207,13 @@ int ldc_attn_fwd_qrows(const float* Q, const float* K, const float* V, float* O,
 int ldc_attn_fwd_ws_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
                           long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace, long long workspace_bytes,
                           void* stream);
+/* The same with the deferred-rescale threshold given by the caller (tests, measurements).  The kernel keeps, per query, the maximum that
+ * was applied to its O and l accumulators, and rescales them only when a key tile's maximum exceeds it by more than rescale_thr (log2
+ * units, 0 .. 64; probabilities are then at most 2^rescale_thr).  ldc_attn_fwd_ws_qrows is this call with the library's threshold (8);
+ * 0 makes the accumulators follow every new maximum.  Results agree to fp32 rounding whatever the threshold. */
+int ldc_attn_fwd_ws_qrows_thr(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                              long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace,
+                              long long workspace_bytes, float rescale_thr, void* stream);
 
 /* (ABI 2: the second-generation split attention - ldc_attn_pack_bf16x3 / ldc_attn_fwd_packed_bf16x3 / ldc_attn_packed_bytes, a
  * pack pass writing LDS tile images + the attention on them - was removed; ldc_attn_qkv_prepare_split / the fused QKV epilogue +

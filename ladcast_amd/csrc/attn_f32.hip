@@ -55,6 +55,7 @@ struct AttnArgs {
   float* ws;
   unsigned* counters;
   int Sq;  // queries = token rows [0, Sq) (1 <= Sq <= S); keys / values = all S rows.  nq = query blocks of Sq
+  float thr;  // deferred rescale: O and l are rescaled only when a query's tile maximum exceeds the applied maximum by more than thr (log2 units)
 };
 constexpr int SLAB_FLOATS = 66 * 256;  // [64 O values + m + l][256 threads of key group 0]
 
@@ -89,6 +90,7 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_f32_ke
   const int half = lane >> 5;
   const int l31 = lane & 31;
   const int S = p.S;
+  const float thr = p.thr;
   // XCD-aware placement (speed only): the query blocks of one (batch, head) re-read the same K/V (2.3 MB at
   // S = 2250), so lay the 1-D grid out as [batch][head][query block] and give each XCD a contiguous run of it
   // (blocks are dealt round-robin over the 8 XCDs; bijective remap for any grid size).
@@ -142,21 +144,29 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_f32_ke
     }
   }
 
-  // staging map: thread t moves float4 column c4 = t&31 of key rows (t>>5) + 8*i
+  // staging map: thread t moves float4 column c4 = t&31 of key rows (t>>5) + 8*i.  A whole tile is addressed as a wave-uniform row base
+  // (scalar arithmetic) plus ONE per-thread byte offset, with no per-row bounds branch; only the tile that crosses S clamps its rows to the
+  // last key (their scores are masked below, so their probabilities are exactly 0 and the duplicated V rows never count)
   const int c4 = tid & 31;
   const int kr0 = tid >> 5;
-  float4 rk[4], rv[4];
+  const unsigned boff = (static_cast<unsigned>(kr0) * static_cast<unsigned>(ld) + static_cast<unsigned>(c4) * 4u) * 4u;
+  typedef float f4s __attribute__((ext_vector_type(4)));  // (native vectors: the two-armed gload keeps them in registers)
+  f4s rk[4], rv[4];
   auto gload = [&](int key0) {
+    if (key0 + KT <= S) {  // (wave-uniform)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int key = key0 + kr0 + 8 * i;
-      if (key < S) {
-        const long long off = static_cast<long long>(key) * ld + c4 * 4;
-        rk[i] = *reinterpret_cast<const float4*>(Kg + off);
-        rv[i] = *reinterpret_cast<const float4*>(Vg + off);
-      } else {
-        rk[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int i = 0; i < 4; ++i) {
+        const long long row = static_cast<long long>(key0 + 8 * i) * ld;  // uniform
+        rk[i] = *reinterpret_cast<const f4s*>(reinterpret_cast<const char*>(Kg + row) + boff);
+        rv[i] = *reinterpret_cast<const f4s*>(reinterpret_cast<const char*>(Vg + row) + boff);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = key0 + kr0 + 8 * i;
+        const long long off = static_cast<long long>(key < S ? key : S - 1) * ld + c4 * 4;
+        rk[i] = *reinterpret_cast<const f4s*>(Kg + off);
+        rv[i] = *reinterpret_cast<const f4s*>(Vg + off);
       }
     }
   };
@@ -166,8 +176,8 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_f32_ke
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int key = kr0 + 8 * i;
-      *reinterpret_cast<float4*>(Ks + key * KP + c4 * 4) = rk[i];
-      *reinterpret_cast<float4*>(Vs + key * HD + c4 * 4) = rv[i];
+      *reinterpret_cast<f4s*>(Ks + key * KP + c4 * 4) = rk[i];
+      *reinterpret_cast<f4s*>(Vs + key * HD + c4 * 4) = rv[i];
     }
   };
 
@@ -283,23 +293,28 @@ __global__ __launch_bounds__(256 * NGRP, NGRP == 1 ? 2 : 1) void attn_fwd_f32_ke
 #pragma unroll
     for (int r = 1; r < 16; ++r) m_t = fmaxf(m_t, s[r]);
     m_t = fmaxf(m_t, __shfl_xor(m_t, 32, 64));
-    const float m_new = fmaxf(m_run, m_t);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);  // (v_exp_f32: arguments <= 0; what would be denormal is 0)
-    float rs = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      s[r] = __builtin_amdgcn_exp2f(s[r] - m_new);
-      rs += s[r];
-    }
-    rs += __shfl_xor(rs, 32, 64);
-    l_run = l_run * alpha + rs;
-    m_run = m_new;
-    if (!__all(alpha == 1.0f)) {
+    // deferred rescale: m_run is the maximum that was APPLIED to O and l.  They are rescaled only when some query of the wave saw a tile
+    // maximum more than thr above it (P <= 2^thr; P, l and O are fp32, so only rounding changes) - about once per sweep instead of on most
+    // tiles.  The decision covers the whole tile: its P is exponentiated below, the previous tile's P.V is complete, nothing is pending at
+    // the old maximum.  The group merge and the piece merge below use m_run, the applied maximum.
+    if (!__all(m_t - m_run <= thr)) {
+      const float m_new = fmaxf(m_run, m_t);
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);  // (v_exp_f32: arguments <= 0; what would be denormal is 0)
 #pragma unroll
       for (int d = 0; d < 4; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+      l_run *= alpha;
+      m_run = m_new;
     }
+    float rs = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      s[r] = __builtin_amdgcn_exp2f(s[r] - m_run);
+      rs += s[r];
+    }
+    rs += __shfl_xor(rs, 32, 64);
+    l_run += rs;
 
 #endif
     // ---- O^T += V^T . P^T ------------------------------------------------------
@@ -474,17 +489,20 @@ constexpr long long BAL_COUNTER_BYTES = BAL_MAX_UNITS * 4;
 extern "C" long long ldc_attn_fwd_workspace_bytes(void) {
   return BAL_COUNTER_BYTES + 2LL * BAL_G * SLAB_FLOATS * static_cast<long long>(sizeof(float));
 }
+// deferred rescale: P <= 2^8.  Measured on the 216-unit launch (profiles/attn_f32_trims.log)
+constexpr float RESCALE_THR = 8.0f;
 
 // queries = the first Sq of the S token rows; units = query blocks of Sq x heads x batch, and everything chosen from the unit count (the
 // balanced cut and its ranges, the ticket counters, one or two wave groups) is chosen from that number.  Sq == S is ldc_attn_fwd_ws.
-extern "C" int ldc_attn_fwd_ws_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
-                                     long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace,
-                                     long long workspace_bytes, void* stream) {
+// rescale_thr: the deferred-rescale threshold in log2 units, 0 <= rescale_thr <= 64 (0: O and l follow every new maximum)
+extern "C" int ldc_attn_fwd_ws_qrows_thr(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                                         long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace,
+                                         long long workspace_bytes, float rescale_thr, void* stream) {
   LDC_CHECK_PTR(Q);
   LDC_CHECK_PTR(K);
   LDC_CHECK_PTR(V);
   LDC_CHECK_PTR(O);
-  if (B <= 0 || S <= 0 || H <= 0 || Sq <= 0 || Sq > S) return LDC_ERR_ARG;
+  if (B <= 0 || S <= 0 || H <= 0 || Sq <= 0 || Sq > S || !(rescale_thr >= 0.f && rescale_thr <= 64.f)) return LDC_ERR_ARG;
   LDC_CHECK_ALIGN16(Q);
   LDC_CHECK_ALIGN16(K);
   LDC_CHECK_ALIGN16(V);
@@ -494,6 +512,7 @@ extern "C" int ldc_attn_fwd_ws_qrows(const float* Q, const float* K, const float
   AttnArgs p{Q, K, V, O, S, H, ld_qkv, ldo, qkv_bs, o_bs,
              0.08838834764831845f * 1.4426950408889634f};  // 1/sqrt(128) * log2(e)
   p.Sq = Sq;
+  p.thr = rescale_thr;
   p.nq = ldc_cdiv(Sq, QB);
   p.kbias = key_bias;
   p.nt = ldc_cdiv(S, KT);
@@ -538,6 +557,13 @@ extern "C" int ldc_attn_fwd_ws_qrows(const float* Q, const float* K, const float
   if (two) hipLaunchKernelGGL(attn_fwd_f32_kernel<2>, grid, dim3(512), lds, static_cast<hipStream_t>(stream), p);
   else hipLaunchKernelGGL(attn_fwd_f32_kernel<1>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), p);
   return ldc_launch_status();
+}
+
+extern "C" int ldc_attn_fwd_ws_qrows(const float* Q, const float* K, const float* V, float* O, int B, int S, int Sq, int H, int ld_qkv,
+                                     long long qkv_bs, int ldo, long long o_bs, const float* key_bias, void* workspace,
+                                     long long workspace_bytes, void* stream) {
+  return ldc_attn_fwd_ws_qrows_thr(Q, K, V, O, B, S, Sq, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias, workspace, workspace_bytes, RESCALE_THR,
+                                   stream);
 }
 
 extern "C" int ldc_attn_fwd_ws(const float* Q, const float* K, const float* V, float* O, int B, int S, int H, int ld_qkv,

@@ -106,6 +106,7 @@ def _load():
         "ldc_attn_fwd_ws": (I, [P, P, P, P, I, I, I, I, L, I, L, P, P, L, P]),
         "ldc_attn_fwd_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P]),
         "ldc_attn_fwd_ws_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P, L, P]),
+        "ldc_attn_fwd_ws_qrows_thr": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P, L, F, P]),
         "ldc_attn_fwd_workspace_bytes": (L, []),
         "ldc_qk_rmsnorm_rope": (I, [P, P, I, I, I, I, I, L, P, P, F, P, P, P]),
         "ldc_sphere_conv_nhwc_split": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, L, P]),
@@ -362,13 +363,22 @@ def _attn_f32_workspace(device):
     return _workspace("attn_fwd", device, lib.ldc_attn_fwd_workspace_bytes(), init="zero")
 
 
-def attn_fwd(Q, K, V, O, *, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias=None, use_workspace=True, Sq=None):
+def attn_fwd(Q, K, V, O, *, B, S, H, ld_qkv, qkv_bs, ldo, o_bs, key_bias=None, use_workspace=True, Sq=None, rescale_thr=None):
     """exact-fp32 attention on fp32 q / k / v views (ldc_attn_fwd_ws); key_bias: [S] additive score bias per key (or None).
     use_workspace=False: never the balanced schedule (ldc_attn_fwd; A/B, tests).  Sq: the queries are the first Sq token rows only
-    (keys / values: all S; rows >= Sq of O untouched; ldc_attn_fwd_qrows / _ws_qrows)"""
+    (keys / values: all S; rows >= Sq of O untouched; ldc_attn_fwd_qrows / _ws_qrows).  rescale_thr (tests, measurements): the deferred-rescale
+    threshold of ldc_attn_fwd_ws_qrows_thr in log2 units (0: rescale at every new maximum); None: the library's"""
     _dev(Q, K, V, O, key_bias)
     if key_bias is not None and key_bias.numel() < S:
         raise ValueError("key_bias must hold one value per key")
+    if rescale_thr is not None:
+        ws = _attn_f32_workspace(Q.device) if use_workspace else None
+        st = lib.ldc_attn_fwd_ws_qrows_thr(_p(Q), _p(K), _p(V), _p(O), B, S, S if Sq is None else Sq, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias),
+                                           _p(ws), 0 if ws is None else ws.numel() * 4, float(rescale_thr), _stream())
+        if ws is not None and st != 0 and not torch.cuda.is_current_stream_capturing():
+            ws.zero_()
+        _check(st, "ldc_attn_fwd_ws_qrows_thr")
+        return
     if not use_workspace:
         if Sq is None:
             _check(lib.ldc_attn_fwd(_p(Q), _p(K), _p(V), _p(O), B, S, H, ld_qkv, qkv_bs, ldo, o_bs, _p(key_bias), _stream()), "ldc_attn_fwd")
