@@ -712,6 +712,37 @@ int ldc_rollout_events(const float* forecast, long long member_stride, long long
                        long long clim_channel_stride, const int* clim_slot, const float* lat_weight, int M, int C, int L, int H, int W,
                        const ldc_events_desc* desc, int* hist_count, float* hist_weight, int* n_invalid, int L_total, int l_off,
                        void* workspace, long long workspace_bytes, void* stream);
+/* Neighbourhood verification of the same threshold events for every lead time of a decode batch (additive under ABI 5; fss.hip,
+ * DESIGN.md section 8.6): the additive sufficient statistics of the fractions skill score (Roberts & Lean 2008) per (event,
+ * neighbourhood radius, lead time).  ladcast_amd.evaluate.fss_scores derives the scores on the host in float64; sums of several initial
+ * times add.  Not in the reference.  Every argument up to desc exactly as ldc_rollout_events, and the classification of a grid point q
+ * of event e - n(q) in 0 .. M, o(q) in {0, 1}, valid(q) - is the one documented there (one shared device function).  1 <= M <= 1024.
+ * radii: HOST array of S <= LDC_FSS_SCALES_MAX radii r >= 0 in GRID POINTS (copied into the launch); the window is (2 r + 1) x (2 r + 1)
+ *   points: rows i - r .. i + r clipped to 0 .. H - 1, columns j - r .. j + r modulo W (longitude is periodic).  Its width in
+ *   kilometres shrinks towards the poles; nothing corrects for that.
+ * Over the valid points of the window of centre p = (i, j), exact integers:  N = #valid, Sn = sum n(q), So = sum o(q).  A centre
+ * contributes when p itself is valid (N >= 1): land centres of SST are not scored, land neighbours enter neither fraction.  Per
+ * contributing centre, fp64, every operation rounded on its own, w = double(lat_weight[i]):
+ *   Pf = double(Sn) / (double(M) * double(N)),  Po = double(So) / double(N),  a = w * Pf,  b = w * Po,  d = Pf - Po
+ *   fss_sums  [E][S][L_total][6] fp64: the sums over the contributing centres of  w, a, b, a * Pf, b * Po, (w * d) * d  - all
+ *     non-negative; FSS = 1 - s5 / (s3 + s4).  r = 0 makes s5 the numerator of the Brier score of ldc_rollout_events.
+ *   n_invalid [E][L_total] int32: the centres left out, equal to ldc_rollout_events' n_invalid.
+ *   Columns l_off .. l_off + L - 1 of both outputs are written, the others left alone.  No atomics: run-to-run bit-equal.
+ * workspace: ldc_rollout_fss_workspace_bytes(M, E, S, L, H, W) bytes of device scratch, 8-byte aligned (0 for arguments the call
+ *   refuses): 16 bytes per point and (event, lead time) - a packed word and a summed-area table entry of three uint32 - plus the
+ *   workgroup records.
+ * LDC_ERR_ARG: everything ldc_rollout_events refuses, radii == NULL, S outside 1 .. LDC_FSS_SCALES_MAX, a negative radius, a window
+ * with 2 r + 1 > W (it would meet itself; 2 r + 1 >= H is served: every row) or a workspace that is too small; LDC_ERR_UNSUPPORTED:
+ * M > 1024, L > 65535, H * W > 2^24 or M * H * W > 2^31 (Sn is held in uint32); LDC_ERR_ALIGN: workspace or fss_sums not 8-byte
+ * aligned.  Nothing is launched on an error. */
+#define LDC_FSS_SCALES_MAX 16
+long long ldc_rollout_fss_workspace_bytes(int M, int E, int S, int L, int H, int W);
+int ldc_rollout_fss(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride, const float* mean,
+                    const float* std_, float target_std, const float* truth, long long truth_slot_stride, long long truth_channel_stride,
+                    const int* truth_slot, const float* clim, long long clim_slot_stride, long long clim_channel_stride,
+                    const int* clim_slot, const float* lat_weight, int M, int C, int L, int H, int W, const ldc_events_desc* desc,
+                    const int* radii, int S, double* fss_sums, int* n_invalid, int L_total, int l_off, void* workspace,
+                    long long workspace_bytes, void* stream);
 /* Regional ensemble scores for every lead time of a decode batch in one launch (additive under ABI 5; regional.hip, DESIGN.md section
  * 8.5): for up to 32 regions that may overlap, the additive sufficient statistics of bias, RMSE, spread, spread-skill ratio, CRPS and
  * ACC per (region, channel, lead time).  ladcast_amd.evaluate.regional_scores derives the scores on the host in float64; sums of several

@@ -22,7 +22,7 @@
 //   finish launch, one workgroup per (event, lead time): bin b adds the records' entries in record order, thread 0 the invalid counts.
 #include <math.h>
 
-#include "ensemble_common.h"
+#include "events_common.h"
 
 namespace {
 
@@ -54,18 +54,11 @@ struct EvArgs {
   ldc_events_desc d;
 };
 
-// DIR > 0: a > thr; DIR < 0: a < thr.  A NaN compares false either way (such a point is not valid and is never counted).
-template <int DIR>
-__device__ __forceinline__ int hit(float a, float thr) {
-  if constexpr (DIR > 0) return a > thr ? 1 : 0;
-  else return a < thr ? 1 : 0;
-}
-
-// NMAX > 0: M <= NMAX members loaded into registers before they are compared; NMAX == 0: any M, streamed
+// NMAX > 0: M <= NMAX members loaded into registers before they are compared; NMAX == 0: any M, streamed (classify_event_point,
+// events_common.h: the per-point classification that fss.hip shares)
 template <int NMAX, bool INV, int DIR>
 __device__ __forceinline__ void events_body(const EvArgs& a, int* s_key, float* s_w, int* red_i) {
   constexpr int KB = NMAX > 0 ? 1 : KB_MAX;
-  constexpr int NX = NMAX > 0 ? NMAX : 1;
   const int e = blockIdx.y, l = blockIdx.z;
   const int M = a.M;
   const int HW = a.H * a.W;
@@ -97,32 +90,9 @@ __device__ __forceinline__ void events_body(const EvArgs& a, int* s_key, float* 
     const float t = tbase[pp];
     const float w = a.lat_w[pp / a.W];
     const float cl = anom ? cbase[pp] : 0.f;
-    int n = 0;
-    bool nan_m = false;
-    if constexpr (NMAX > 0) {
-      float x[NX];
-#pragma unroll
-      for (int i = 0; i < NX; ++i) x[i] = i < M ? f[static_cast<long long>(i) * a.fc_ms] : 0.f;
-#pragma unroll
-      for (int i = 0; i < NX; ++i)
-        if (i < M) {
-          float v = x[i];
-          if constexpr (INV) v = inv_norm(v, nrm);
-          nan_m = nan_m || (v != v);
-          const float u = anom ? v - cl : v;
-          n += hit<DIR>(u, thr);
-        }
-    } else {
-      for (int i = 0; i < M; ++i) {
-        float v = f[static_cast<long long>(i) * a.fc_ms];
-        if constexpr (INV) v = inv_norm(v, nrm);
-        nan_m = nan_m || (v != v);
-        const float u = anom ? v - cl : v;
-        n += hit<DIR>(u, thr);
-      }
-    }
-    const int o = hit<DIR>(anom ? t - cl : t, thr);
-    const bool valid = in && !nan_m && t == t && cl == cl;
+    const EventPoint pt = classify_event_point<NMAX, INV, DIR>(f, a.fc_ms, M, t, cl, anom, thr, nrm);
+    const int n = pt.n, o = pt.o;
+    const bool valid = in && pt.valid;
     n_inv += (in && !valid) ? 1 : 0;
     __syncthreads();  // the walk of the tile before is over
     s_key[tid] = valid ? 2 * n + o : -1;

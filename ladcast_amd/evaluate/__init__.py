@@ -1,4 +1,4 @@
-from .utils import (EVENT_SCORE_NAMES, VALIDATION_SCORE_NAMES, Event, empty_events, empty_products, event_scores, rollout_events, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
+from .utils import (EVENT_SCORE_NAMES, FSS_SCORE_NAMES, VALIDATION_SCORE_NAMES, Event, empty_events, empty_fss, empty_products, event_scores, fss_scores, rollout_events, rollout_fss, ensemble_scores, get_acc, get_crps, get_lat_weights_from_lat_tensor,
                     get_normalized_lat_weights_based_on_cos, pointwise_crps_skill, pointwise_crps_spread, rollout_products, rollout_reliability, rollout_scores, rollout_spectrum,
                     validation_scores)
 from .regional import NAMED_REGIONS, REGIONAL_SCORE_NAMES, Region, empty_regional, region_mask, regional_scores, rollout_regional
@@ -9,7 +9,7 @@ _DENOISE_NAMES = ("denoising_loss", "evaluate_denoising_loss", "push_forward_pla
 _PRODUCTS_NAMES = ("products_of_latent_rollout",)  # products', likewise
 __all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
            "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores", "rollout_spectrum",  # also runs
-           "validation_scores", "empty_products", "rollout_products", "EVENT_SCORE_NAMES", "Event", "empty_events", "event_scores", "rollout_events", "NAMED_REGIONS", "REGIONAL_SCORE_NAMES",
+           "validation_scores", "empty_products", "rollout_products", "EVENT_SCORE_NAMES", "Event", "empty_events", "event_scores", "rollout_events", "FSS_SCORE_NAMES", "empty_fss", "fss_scores", "rollout_fss", "NAMED_REGIONS", "REGIONAL_SCORE_NAMES",
            "Region", "empty_regional", "region_mask", "regional_scores", "rollout_regional", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES]  # as `python -m`
 
 

@@ -21,6 +21,11 @@ events (`ldc_rollout_events`, not in the reference): the histogram of "members s
 over the initial times (`event_hist.npy`, `event_hist_weighted.npy` (E, lead time, ens + 1, 2)), `event_n_invalid.npy` (init time, E, lead
 time), `events.json`, and from the pooled histogram `event_brier.npy`, `event_bss.npy`, `event_reliability.npy`, `event_resolution.npy`,
 `event_uncertainty.npy`, `event_roc_area.npy` (E, lead time).
+`--fss_scales R [R ...]` (with events) verifies the same events in neighbourhoods of (2 R + 1) x (2 R + 1) GRID POINTS (`ldc_rollout_fss`,
+not in the reference; periodic in longitude, clipped at the poles, not corrected for the convergence of the meridians): the sums of the
+fractions skill score pooled over the initial times (`event_fss_sums.npy` (E, scale, lead time, 6)), `event_fss.npy`,
+`event_fss_target.npy`, `event_fss_obs_fraction.npy`, `event_fss_freq_bias.npy` (E, scale, lead time), `event_fss_useful_scale.npy` (E, lead
+time: the smallest radius whose FSS reaches 0.5 + obs_fraction / 2, or -1), and `fss_radii` / `fss_width_deg` in `events.json`.
 `--region NAME` (any number of times, from `NAMED_REGIONS`), `--region_box NAME LAT0 LAT1 LON0 LON1`, `--region_surface NAME land|sea`
 (with `--land_sea_mask_path`) break the scores down by region (`ldc_rollout_regional`, not in the reference): every region in one pass
 per decode batch, the additive sums pooled over the initial times (`regional_sums.npy` (R, C, lead time, 10), `regional_counts.npy`),
@@ -44,14 +49,18 @@ import torch
 from .track import LEVELS, NUM_ATM_VARS, VARIABLE_NAMES, mean_std_from_json
 from .regional import (COUNT_NAMES, SUM_NAMES, REGIONAL_KEYS, REGIONAL_SCORE_NAMES, NAMED_REGIONS, Region, empty_regional, mask_words, region_mask as make_region_mask,
                        region_metadata, regional_scores, rollout_regional)
-from .utils import (SCORE_NAMES, SPECTRUM_NAMES, Event, empty_events, empty_reliability, empty_spectrum, event_scores,
-                    get_normalized_lat_weights_based_on_cos, rollout_events, rollout_reliability, rollout_scores, rollout_spectrum)
+from .utils import (MAX_FSS_SCALES, SCORE_NAMES, SPECTRUM_NAMES, Event, _radius_list, empty_events, empty_fss, empty_reliability, empty_spectrum, event_scores,
+                    fss_scores, get_normalized_lat_weights_based_on_cos, rollout_events, rollout_fss, rollout_reliability, rollout_scores,
+                    rollout_spectrum)
 
 SST_CHANNEL_IDX = 82
 CLIMATOLOGY_HOURS = (0, 6, 12, 18)
 RELIABILITY_KEYS = ("ens_var", "ssr", "rank_hist", "rank_hist_weighted", "n_invalid")  # what `--reliability` adds
 SPECTRUM_KEYS = SPECTRUM_NAMES + ("spec_n_invalid",)  # what `--spectrum` adds
 EVENTS_KEYS = ("event_hist", "event_hist_weighted", "event_n_invalid")  # what `--event` / `--event_anomaly` add to one initial time
+FSS_KEYS = ("event_fss_sums", "event_fss_n_invalid")  # what `--fss_scales` adds to one initial time
+FSS_FILE_SCORES = dict(event_fss="fss", event_fss_target="fss_target", event_fss_obs_fraction="obs_fraction",
+                       event_fss_freq_bias="freq_bias")  # <file>.npy: the score of `fss_scores`, from the pooled sums
 EVENT_FILE_SCORES = ("brier", "bss", "reliability", "resolution", "uncertainty", "roc_area")  # event_<name>.npy, from the pooled histogram
 
 
@@ -112,7 +121,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                          total_num_steps: Optional[int] = None, crop_init: bool = False, force_ens_size: Optional[int] = None,
                          decode_batch_frames: Optional[int] = None, reliability: bool = False, spectrum: bool = False,
                          spectrum_row_weight: Optional[torch.Tensor] = None, events: Optional[Sequence] = None,
-                         regions: Optional[Sequence] = None, region_mask=None) -> Dict[str, torch.Tensor]:
+                         regions: Optional[Sequence] = None, region_mask=None, fss_radii: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -137,6 +146,11 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     while it is on the device and the result gains `EVENTS_KEYS`: `event_hist` (E, total_num_steps, ens + 1, 2) int32, `event_hist_weighted`
     the same in fp32 and `event_n_invalid` (E, total_num_steps) int32 (`rollout_events`).  An anomaly event with `clim` None is a
     ValueError.  The five scores, the reliability outputs and the spectrum outputs are the bits of a call without it.
+
+    `fss_radii`: with `events`, a sequence of neighbourhood radii in grid points; every decode batch also goes through `ldc_rollout_fss`
+    while it is on the device and the result gains `FSS_KEYS`: `event_fss_sums` (E, S, total_num_steps, 6) float64 and
+    `event_fss_n_invalid` (E, total_num_steps) int32 (`rollout_fss`; columns past the last lead time are zeros).  Without `events` it is a
+    ValueError.  Every other output is the bits of a call without it.
 
     `regions`: a sequence of `Region` (or an int: their number), with `region_mask` the (H, W) uint32 mask of which bit r marks region
     r (`regional.region_mask`; default: built from `regions` on `row_latitudes(H)` and the longitudes 0, 360 / W, ...); every decode
@@ -167,6 +181,9 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     events = [Event(*ev) for ev in events] if events else None
     if events and clim is None and any(ev.anomaly for ev in events):
         raise ValueError("an anomaly event needs the climatology (clim)")
+    if fss_radii is not None and not events:
+        raise ValueError("fss_radii needs events: the neighbourhood scores verify threshold events")
+    fss_radii = None if fss_radii is None else list(fss_radii)
     n_regions = 0
     if regions is not None or region_mask is not None:
         if regions is None:
@@ -193,7 +210,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             raise ValueError("spectrum_row_weight must be non-negative (0 leaves a row out) and not NaN")
         spec_w = spec_w.to(dev, torch.float32)
     per = max(1, int(decode_batch_frames) // ens) if decode_batch_frames else 1  # lead times per decoder call: a lead time's members stay together
-    scores = rel = spec = evs = reg = reg_words = None
+    scores = rel = spec = evs = fss = reg = reg_words = None
     for s0 in range(0, T, per):
         nl = min(per, T - s0)
         x = latents[:, :, s0 : s0 + nl].permute(2, 0, 1, 3, 4).reshape(nl * ens, C, h, w).contiguous()  # lead-major, then member
@@ -218,6 +235,12 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             rollout_events(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, events, clim=clim,
                            clim_slots=None if clim is None else c_slots[s0 : s0 + nl], lead_dim=0, mean=mean_d, std=std_d,
                            truth_slot=t_slots[s0 : s0 + nl], out=evs, l_off=s0)
+        if fss_radii is not None:
+            if fss is None:
+                fss = empty_fss(len(events), len(_radius_list(fss_radii, y.shape[3])), total, dev)
+            rollout_fss(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, events, fss_radii, clim=clim,
+                        clim_slots=None if clim is None else c_slots[s0 : s0 + nl], lead_dim=0, mean=mean_d, std=std_d,
+                        truth_slot=t_slots[s0 : s0 + nl], out=fss, l_off=s0)
         if n_regions:
             if reg is None:
                 Hd, Wd = y.shape[2], y.shape[3]
@@ -236,6 +259,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
         res.update({k: spec[k].cpu() for k in SPECTRUM_NAMES}, spec_n_invalid=spec["n_invalid"].cpu())
     if events:
         res.update({k: evs[k].cpu() for k in EVENTS_KEYS})
+    if fss is not None:
+        res.update({k: fss[k].cpu() for k in FSS_KEYS})
     if n_regions:
         res.update({k: reg[k].cpu() for k in REGIONAL_KEYS})
     return res
@@ -332,6 +357,36 @@ def _gather_events(evs: dict, res, time_str: str, total_num_steps: int, E: int) 
     evs["event_n_invalid"].append(a["event_n_invalid"].astype(np.int32))
     evs["event_hist"] += a["event_hist"].astype(np.int64)
     evs["event_hist_weighted"] += a["event_hist_weighted"].astype(np.float64)
+
+
+def _gather_fss(fss: dict, res, time_str: str, total_num_steps: int, E: int, S: int) -> None:
+    """one initial time's `FSS_KEYS` into the run's: the sums are added over the initial times on the host in float64,
+    `event_fss_n_invalid` (int32) is kept per initial time"""
+    missing = [k for k in FSS_KEYS if k not in res]
+    if missing:
+        raise ValueError(f"{time_str}: --fss_scales needs {missing} from the scorer")
+    s, n = np.asarray(res["event_fss_sums"], dtype=np.float64), np.asarray(res["event_fss_n_invalid"])
+    if s.shape != (E, S, total_num_steps, 6) or n.shape != (E, total_num_steps):
+        raise ValueError(f"{time_str}: fss arrays of shapes {s.shape} and {n.shape}, expected ({E}, {S}, {total_num_steps}, 6) and "
+                         f"({E}, {total_num_steps})")
+    fss["event_fss_sums"] = s.copy() if fss["event_fss_sums"] is None else fss["event_fss_sums"] + s
+    fss["event_fss_n_invalid"].append(n.astype(np.int32))
+
+
+def parse_fss_scales(values) -> List[int]:
+    """`--fss_scales R [R ...]` -> the radii in grid points as given: 1 .. 16 whole numbers >= 0, no two equal (that they fit the
+    grid, 2 R + 1 <= W, is checked where W is known: `rollout_fss`)"""
+    try:
+        radii = [int(str(v)) for v in values]
+    except ValueError:
+        raise ValueError(f"--fss_scales {' '.join(map(str, values))}: the radii are whole numbers of grid points") from None
+    if not 1 <= len(radii) <= MAX_FSS_SCALES:
+        raise ValueError(f"--fss_scales: {len(radii)} radii, 1 .. {MAX_FSS_SCALES} are served")
+    if any(r < 0 for r in radii):
+        raise ValueError(f"--fss_scales {radii}: a radius must not be negative")
+    if len(set(radii)) != len(radii):
+        raise ValueError(f"--fss_scales {radii}: the radii must differ")
+    return radii
 
 
 def _gather_regional(regs: dict, res, time_str: str, total_num_steps: int, R: int, per_init: bool) -> None:
@@ -443,6 +498,12 @@ def main(argv=None, score: Optional[Callable] = None):
     `event_reliability.npy`, `event_resolution.npy`, `event_uncertainty.npy`, `event_roc_area.npy` (E, lead time) float64: `event_scores`
     of the pooled weighted histogram.  Without the flags the launches and the files are those of a run before they existed.
 
+    `--fss_scales R [R ...]` (needs an event flag; the scorer then returns `FSS_KEYS` too) adds `event_fss_sums.npy` (E, scale, lead time, 6)
+    float64, summed over the initial times, `event_fss_n_invalid.npy` (init time, E, lead time) int32, `event_fss.npy`,
+    `event_fss_target.npy`, `event_fss_obs_fraction.npy`, `event_fss_freq_bias.npy` (E, scale, lead time) and `event_fss_useful_scale.npy`
+    (E, lead time) int64: `fss_scores` of the pooled sums; `events.json` gains `fss_radii` (grid points) and `fss_width_deg` (the
+    window's width (2 R + 1) 360 / W in degrees of longitude and latitude; in kilometres it shrinks towards the poles).
+
     `--region NAME` (from `NAMED_REGIONS`), `--region_box NAME LAT0 LAT1 LON0 LON1` (each any number of times; named regions first) and
     `--region_surface NAME land|sea` with `--land_sea_mask_path` (.npy (H_in, W), land where >= 0.5; rows cropped as the truth's) make
     the scorer return `REGIONAL_KEYS` too.  The sums are pooled over the initial times on the host (float64, counts in int64):
@@ -480,6 +541,8 @@ def main(argv=None, score: Optional[Callable] = None):
                     help="verify the event 'CHANNEL above (gt) / below (lt) VALUE' (physical units); may be given several times")
     ap.add_argument("--event_anomaly", nargs=3, action="append", default=[], metavar=("CHANNEL", "gt|lt", "VALUE"),
                     help="the same on CHANNEL minus its climatology")
+    ap.add_argument("--fss_scales", nargs="+", default=None, metavar="R",
+                    help="also verify the events in neighbourhoods of (2 R + 1) x (2 R + 1) grid points (fractions skill score); needs --event / --event_anomaly")
     ap.add_argument("--region", action="append", default=[], metavar="NAME", help="break the scores down by this named region; may be given several times")
     ap.add_argument("--region_box", nargs=5, action="append", default=[], metavar=("NAME", "LAT0", "LAT1", "LON0", "LON1"),
                     help="a region of your own: latitudes LAT0 .. LAT1 (inclusive), longitudes LON0 .. LON1 east (LON0 > LON1: across 0 degrees)")
@@ -508,6 +571,13 @@ def main(argv=None, score: Optional[Callable] = None):
         from .validate_AR import column_names
 
         events, events_meta = parse_events(args.event, args.event_anomaly, column_names(args.variable_names, args.levels, args.num_atm_vars))
+
+    fss_radii = None
+    if args.fss_scales is not None:
+        if not events:
+            raise ValueError("--fss_scales needs --event or --event_anomaly")
+        fss_radii = parse_fss_scales(args.fss_scales)
+    grid_w = None  # points per row, where the data tell it
 
     regions = parse_regions(args.region, args.region_box, args.region_surface)
     if any(r.surface for r in regions) and args.land_sea_mask_path is None:
@@ -544,6 +614,7 @@ def main(argv=None, score: Optional[Callable] = None):
         if args.load_ds_in_memory:  # both tables resident on the device; otherwise planes are staged per initial time
             truth = torch.from_numpy(np.ascontiguousarray(truth, dtype=np.float32)).to("cuda")
             clim = torch.from_numpy(np.ascontiguousarray(clim, dtype=np.float32)).to("cuda")
+        grid_w = int(truth.shape[-1])
         lat_w = lat_weights_for(H)
         spec_w = spectrum_band_weights(lat_w, row_latitudes(H), args.spectrum_lat_band) if args.spectrum else None
         reg_mask = None
@@ -554,13 +625,15 @@ def main(argv=None, score: Optional[Callable] = None):
             return score_latent_rollout(path, model, mean_t, std_t, truth, t_slots, clim, c_slots, lat_w, sst_channel=args.sst_channel_idx,
                                         total_num_steps=total_num_steps, crop_init=args.crop_init, force_ens_size=args.force_ens_size,
                                         decode_batch_frames=args.decode_batch_frames, reliability=args.reliability, spectrum=args.spectrum,
-                                        spectrum_row_weight=spec_w, events=events or None, regions=regions or None, region_mask=reg_mask)
+                                        spectrum_row_weight=spec_w, events=events or None, regions=regions or None, region_mask=reg_mask,
+                                        fss_radii=fss_radii)
 
     os.makedirs(args.output, exist_ok=True)
     gathered = {k: [] for k in SCORE_NAMES}
     rel = dict(ens_var=[], ssr=[], n_invalid=[], rank_hist=None, rank_hist_weighted=None)
     spec = {k: [] for k in SPECTRUM_KEYS}
     evs = dict(event_n_invalid=[], event_hist=None, event_hist_weighted=None)
+    fss = dict(event_fss_sums=None, event_fss_n_invalid=[])
     regs = dict(regional_sums=None, regional_counts=None, per_init=[])
     for i, (time_str, path) in enumerate(files):
         print(f"processing time_str: {time_str}, remaining: {len(files) - i - 1}")
@@ -579,6 +652,8 @@ def main(argv=None, score: Optional[Callable] = None):
             _gather_spectrum(spec, res, time_str, total_num_steps)
         if events:
             _gather_events(evs, res, time_str, total_num_steps, len(events))
+        if fss_radii is not None:
+            _gather_fss(fss, res, time_str, total_num_steps, len(events), len(fss_radii))
         if regions:
             _gather_regional(regs, res, time_str, total_num_steps, len(regions), args.region_per_init)
     out = {k: np.stack(v) for k, v in gathered.items()}
@@ -590,8 +665,15 @@ def main(argv=None, score: Optional[Callable] = None):
         out.update(event_n_invalid=np.stack(evs["event_n_invalid"]), event_hist=evs["event_hist"], event_hist_weighted=evs["event_hist_weighted"])
         sc = event_scores(evs["event_hist_weighted"])
         out.update({f"event_{k}": np.asarray(sc[k], dtype=np.float64) for k in EVENT_FILE_SCORES})
+        meta = dict(events=events_meta)
+        if fss_radii is not None:
+            out.update(event_fss_sums=fss["event_fss_sums"], event_fss_n_invalid=np.stack(fss["event_fss_n_invalid"]))
+            sc = fss_scores(fss["event_fss_sums"], fss_radii)
+            out.update({name: np.asarray(sc[k], dtype=np.float64) for name, k in FSS_FILE_SCORES.items()},
+                       event_fss_useful_scale=np.asarray(sc["useful_scale"], dtype=np.int64))
+            meta.update(fss_radii=fss_radii, fss_width_deg=None if grid_w is None else [(2 * r + 1) * 360.0 / grid_w for r in fss_radii])
         with open(os.path.join(args.output, "events.json"), "w") as f:
-            json.dump(dict(events=events_meta), f, indent=1)
+            json.dump(meta, f, indent=1)
     if regions:
         out.update(regional_sums=regs["regional_sums"], regional_counts=regs["regional_counts"])
         ens = int(np.load(files[0][1], mmap_mode="r").shape[0])  # the members the sums were taken over: the ssr's (M + 1) / M

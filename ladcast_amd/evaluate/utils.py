@@ -639,3 +639,128 @@ def event_scores(hist_weighted) -> Dict[str, "numpy.ndarray"]:  # noqa: F821
         area = np.where((W1 > 0) & (W0 > 0), area, np.nan)
     return dict(brier=brier, reliability=rel, resolution=res, uncertainty=unc, bss=bss, base_rate=obar, forecast_mean=fmean, roc_area=area,
                 rel_prob=np.broadcast_to(p, on.shape).copy(), rel_obs=on, rel_weight=rel_weight, roc_pofd=pofd, roc_pod=pod)
+
+
+MAX_FSS_SCALES = hip.FSS_SCALES_MAX
+FSS_SUM_NAMES = ("w", "w_pf", "w_po", "w_pf2", "w_po2", "w_d2")  # the six sums of ldc_rollout_fss, in order
+FSS_SCORE_NAMES = ("fss", "fss_target", "obs_fraction", "fcst_fraction", "freq_bias")
+
+
+class FssDict(dict):
+    """{event_fss_sums: (E, S, L_total, 6) float64; event_fss_n_invalid: (E, L_total) int32} over the two device buffers `ldc_rollout_fss`
+    fills: entry [e, s, l] holds the sums of `FSS_SUM_NAMES` over the contributing centres of event e at radius s"""
+
+    def __init__(self, sums, n_invalid):
+        super().__init__(event_fss_sums=sums, event_fss_n_invalid=n_invalid)
+        self._buffers = (sums, n_invalid)
+
+
+def empty_fss(E: int, S: int, L_total: int, device) -> FssDict:
+    """the result of `rollout_fss` before any column is written: zeros"""
+    return FssDict(torch.zeros(E, S, L_total, len(FSS_SUM_NAMES), device=device, dtype=torch.float64),
+                   torch.zeros(E, L_total, device=device, dtype=torch.int32))
+
+
+def _radius_list(radii, W: int):
+    """`radii` -> a list of 1 .. 16 non-negative integers with 2 r + 1 <= W; every mistake is a ValueError"""
+    rs = list(radii.tolist() if isinstance(radii, torch.Tensor) else radii)
+    if not 1 <= len(rs) <= MAX_FSS_SCALES:
+        raise ValueError(f"{len(rs)} radii: ldc_rollout_fss takes 1 .. {MAX_FSS_SCALES} per call")
+    if any(isinstance(r, bool) or int(r) != r for r in rs):
+        raise ValueError(f"radii are whole numbers of grid points, got {rs}")
+    rs = [int(r) for r in rs]
+    if any(r < 0 for r in rs):
+        raise ValueError(f"a radius must not be negative, got {rs}")
+    if any(2 * r + 1 > W for r in rs):
+        raise ValueError(f"radii {rs}: a window of 2 r + 1 points must not be wider than the {W} points of a row (it would meet itself)")
+    return rs
+
+
+@torch.no_grad()
+def rollout_fss(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torch.Tensor, events, radii, *, clim: Optional[torch.Tensor] = None,
+                clim_slots=None, lead_dim: int = 2, mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None,
+                target_std: float = 1.0, truth_slot=None, out: Optional[Dict[str, torch.Tensor]] = None,
+                l_off: int = 0) -> Dict[str, torch.Tensor]:
+    """Neighbourhood verification of threshold events for every lead time in one call (`ldc_rollout_fss`; not in the reference): the
+    sufficient statistics of the fractions skill score (Roberts & Lean 2008).  Every grid point q of event e is classified exactly as in
+    `rollout_events`: n(q) of the M members show the event, the truth does (o(q) = 1) or does not, and q is valid or not.  For a radius r
+    in GRID POINTS the window of a centre p = (i, j) is rows i - r .. i + r clipped to the grid and columns j - r .. j + r modulo W
+    (longitude is periodic); over its valid points N = #valid, Sn = sum n, So = sum o.  A centre contributes when it is valid itself.  In
+    float64, each operation rounded on its own, with w = lat_weight[i]:
+        Pf = Sn / (M N),  Po = So / N,  a = w Pf,  b = w Po,  d = Pf - Po,   terms (w, a, b, a Pf, b Po, (w d) d)
+    `event_fss_sums[e, s, l]` holds the sums of the six terms over the contributing centres, `event_fss_n_invalid[e, l]` the centres left
+    out (equal to `event_n_invalid` of `rollout_events`).  Sums add over initial times; `fss_scores` turns (pooled) sums into the
+    score.  The window is not corrected for the convergence of the meridians: its width in kilometres shrinks towards the poles.
+    1 <= M <= 1024, at most 32 events and 16 radii, 2 r + 1 <= W.
+
+    Every other argument, `out` / `l_off` included, as `rollout_events`.  Returns an `FssDict` of device tensors with L_total = l_off + L
+    columns (unwritten columns: zeros), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_fss`)
+    returned for the same number of events and radii."""
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
+    if not 1 <= M <= MAX_EVENT_MEMBERS:
+        raise ValueError(f"{M} members: ldc_rollout_fss serves 1 .. {MAX_EVENT_MEMBERS}")
+    dev = f.device
+    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
+    c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
+    w = _row_weight(lat_weight, H, dev, "lat_weight")
+    mn, sd = _channel_affine(mean, std, C, dev)
+    desc = hip.events_desc(_event_list(events, C, clim is not None))
+    rs = _radius_list(radii, W)
+    E, S = desc.n_events, len(rs)
+    if l_off < 0:
+        raise ValueError("l_off must not be negative")
+    bufs = None
+    if out is not None:
+        bufs = getattr(out, "_buffers", None)
+        ok = bufs is not None and len(bufs) == 2 and bufs[0].dim() == 4 and all(b.is_contiguous() and b.device == dev for b in bufs)
+        if ok:
+            Lt = bufs[0].shape[2]
+            ok = l_off + L <= Lt and tuple(bufs[0].shape) == (E, S, Lt, len(FSS_SUM_NAMES)) and tuple(bufs[1].shape) == (E, Lt) \
+                and bufs[0].dtype == torch.float64 and bufs[1].dtype == torch.int32
+        if not ok:
+            raise ValueError("out must be the dict an earlier rollout_fss call (or empty_fss) returned for the same number of events and "
+                             "radii, with room for columns l_off .. l_off + L - 1")
+    hip._dev(forecast, truth, clim, lat_weight, mean, std)
+    if bufs is None:
+        bufs = empty_fss(E, S, l_off + L, dev)._buffers
+    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], dev)
+    hip.rollout_fss(f, t, slots[0], c, None if c is None else slots[1], w, desc, rs, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0),
+                    lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs,
+                    clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mn, std=sd, target_std=target_std, L_total=bufs[0].shape[2],
+                    l_off=l_off)
+    return FssDict(*bufs)
+
+
+def fss_scores(sums, radii=None) -> Dict[str, "numpy.ndarray"]:  # noqa: F821
+    """The fractions skill score and its companions from the sums of `rollout_fss`, on the host in float64 (numpy; no device).
+
+    sums: (..., 6) = (s0 .. s5) = the sums of `FSS_SUM_NAMES`, pooled over any number of initial times.
+        fss            1 - s5 / (s3 + s4), NaN where the denominator is 0 (no event in forecast and truth)
+        obs_fraction   s2 / s0            fcst_fraction  s1 / s0            freq_bias  s1 / s2
+        fss_target     0.5 + obs_fraction / 2: the level from which a forecast counts as useful (Roberts & Lean 2008)
+    With `radii` (one per entry of the scale axis, which is axis -3 of `sums`: (..., S, L, 6)) also
+        useful_scale   (..., L) int64: the smallest of `radii` at which fss >= fss_target, -1 where there is none
+    A NaN score compares false.  s0 == 0 gives NaN fractions."""
+    import numpy as np
+
+    s = np.asarray(sums, dtype=np.float64)
+    if s.ndim < 1 or s.shape[-1] != len(FSS_SUM_NAMES):
+        raise ValueError(f"fss sums are (..., {len(FSS_SUM_NAMES)}), got {s.shape}")
+    s0, s1, s2, s3, s4, s5 = (s[..., k] for k in range(6))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = s3 + s4
+        fss = np.where(den > 0, 1.0 - s5 / np.where(den > 0, den, 1.0), np.nan)
+        fss = np.where(np.isnan(den), np.nan, fss)
+        obs, fc, bias = s2 / s0, s1 / s0, s1 / s2
+        target = 0.5 + obs / 2.0
+    res = dict(fss=fss, fss_target=target, obs_fraction=obs, fcst_fraction=fc, freq_bias=bias)
+    if radii is not None:
+        r = np.asarray(list(radii), dtype=np.int64)
+        if s.ndim < 3 or r.ndim != 1 or s.shape[-3] != r.shape[0]:
+            raise ValueError(f"{r.shape[0] if r.ndim == 1 else r.shape} radii for sums of shape {s.shape}: the scale axis is axis -3")
+        with np.errstate(invalid="ignore"):
+            useful = fss >= target  # (..., S, L); NaN compares false
+        big = np.iinfo(np.int64).max
+        cand = np.where(useful, r.reshape((-1, 1)), big).min(-2)
+        res["useful_scale"] = np.where(cand == big, -1, cand)
+    return res

@@ -64,6 +64,9 @@ class ProductsDesc(Structure):  # ldc_products_desc
 EVENTS_MAX, EVENTS_MAX_MEMBERS = 32, 1024  # LDC_EVENTS_MAX, the largest ensemble of ldc_rollout_events
 
 
+FSS_SCALES_MAX, FSS_SUMS = 16, 6  # LDC_FSS_SCALES_MAX, the sums per (event, radius, lead time) of ldc_rollout_fss
+
+
 class EventsDesc(Structure):  # ldc_events_desc
     _fields_ = [("n_events", c_int), ("channel", c_int * EVENTS_MAX), ("dir", c_int * EVENTS_MAX), ("anomaly", c_int * EVENTS_MAX),
                 ("thr", c_float * EVENTS_MAX)]
@@ -134,6 +137,8 @@ def _load():
         "ldc_sizeof_events_desc": (I, []),
         "ldc_rollout_events_workspace_bytes": (L, [I, I, I, I, I]),
         "ldc_rollout_events": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, POINTER(EventsDesc), P, P, P, I, I, P, L, P]),
+        "ldc_rollout_fss_workspace_bytes": (L, [I, I, I, I, I, I]),
+        "ldc_rollout_fss": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, POINTER(EventsDesc), POINTER(c_int), I, P, P, I, I, P, L, P]),
         "ldc_rollout_regional_workspace_bytes": (L, [I, I, I, I, I, I]),
         "ldc_rollout_regional": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, P, I, I, I, I, I, I, P, P, I, I, P, L, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
@@ -543,6 +548,29 @@ def rollout_events(forecast, truth, truth_slot, clim, clim_slot, lat_weight, des
                                   *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
                                   clim_channel_stride, _p(clim_slot), _p(lat_weight), M, C, L, H, W, ctypes.byref(desc), _p(hist_count),
                                   _p(hist_weight), _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_events")
+
+
+def rollout_fss_workspace_bytes(M, E, S, L, H, W):
+    """bytes of device scratch ldc_rollout_fss needs for M members, E events, S radii, L lead times on an H x W grid; 0 for sizes the call
+    refuses"""
+    return int(lib.ldc_rollout_fss_workspace_bytes(M, E, S, L, H, W))
+
+
+def rollout_fss(forecast, truth, truth_slot, clim, clim_slot, lat_weight, desc, radii, fss_sums, n_invalid, *, M, C, L, H, W, member_stride,
+                lead_stride, channel_stride, truth_slot_stride, truth_channel_stride, clim_slot_stride=0, clim_channel_stride=0, mean=None,
+                std=None, target_std=1.0, L_total, l_off=0):
+    """fss_sums (fp64) [E][S][L_total][6]; n_invalid (int32) [E][L_total]: columns l_off .. l_off + L - 1 of L lead times in one call
+    (ladcast_hip.h: ldc_rollout_fss); desc: `events_desc`; radii: S host integers (grid points); truth_slot / clim_slot: device int32 [L]"""
+    _dev(forecast, truth, truth_slot, clim, clim_slot, lat_weight, fss_sums, n_invalid, mean, std)
+    rs = [int(r) for r in radii]
+    if not 1 <= len(rs) <= FSS_SCALES_MAX:
+        raise ValueError(f"{len(rs)} radii: ldc_rollout_fss takes 1 .. {FSS_SCALES_MAX} per call")
+    nbytes = rollout_fss_workspace_bytes(M, desc.n_events, len(rs), L, H, W)
+    ws = _workspace("rollout_fss", forecast.device, max(nbytes, 8), grow=True)
+    _check(lib.ldc_rollout_fss(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                               *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
+                               clim_channel_stride, _p(clim_slot), _p(lat_weight), M, C, L, H, W, ctypes.byref(desc), (c_int * len(rs))(*rs),
+                               len(rs), _p(fss_sums), _p(n_invalid), L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_fss")
 
 
 REGIONS_MAX, REGIONAL_MAX_MEMBERS, REGIONAL_SUMS, REGIONAL_COUNTS = 32, 64, 10, 3  # the limits and the record of ldc_rollout_regional
