@@ -778,6 +778,46 @@ int ldc_rollout_regional(const float* forecast, long long member_stride, long lo
                          long long clim_channel_stride, const int* clim_slot, const float* lat_weight, const unsigned* region_mask, int R,
                          int M, int C, int L, int H, int W, double* sums, int* counts, int L_total, int l_off, void* workspace,
                          long long workspace_bytes, void* stream);
+/* Energy score of a decoded ensemble for every lead time of a decode batch (additive under ABI 5; energy.hip): the
+ * multivariate generalisation of the CRPS, ES = mean_i ||x_i - t|| - 1/2 mean_{i,j} ||x_i - x_j|| with ||.|| the latitude-weighted RMS
+ * norm of a whole field, per (channel, lead time) and per group of channels.  It tells an ensemble of coherent fields from one whose
+ * members are the right marginal distribution shuffled point by point, which no pointwise score can.  Not in the reference.  Addressing
+ * of forecast, inverse normalisation (mean == NULL: physical units), truth table, lat_weight and output columns exactly as
+ * ldc_rollout_regional.  1 <= M <= 256.
+ * Per (channel c, lead l), vectors y_0 .. y_{M-1} the members after the inverse normalisation and y_M the truth:
+ *   a point p is valid when no member and not the truth is NaN; invalid points contribute nothing and are counted; +-inf are ordinary
+ *   values (inf - inf makes the affected entries NaN, as IEEE says)
+ *   D2[a][b] = sum over valid p of double(w_p) * double(sq), d = y_a[p] - y_b[p] (one fp32 subtraction), sq = d * d (one fp32 product),
+ *     w_p = lat_weight[row(p)]; the product is exact: the only roundings are the two fp32 operations and the fp64 additions.  D2 is
+ *     symmetric (entry (b, a) holds the bits of (a, b)) and its diagonal is written as 0 whatever the values are.
+ *   Wv = sum over valid p of double(w_p);  norm(a, b) = sqrt(D2[a][b] / Wv) in fp64 (IEEE sqrt and divide)
+ *   skill = (sum_i norm(i, M)) / M;  spread = (sum_{i != j} norm(i, j)) / (M M);  spread_fair = the same sum / (M (M - 1)), 0 at M == 1;
+ *   the sums run sequentially in (i, j) lexicographic order;  es = skill - 0.5 spread;  es_fair = skill - 0.5 spread_fair;  the four
+ *   are NaN when Wv == 0.  For a single valid point es_fair is the CRPS of that point.
+ * Groups (0 <= G <= 32, may overlap): group_mask DEVICE uint32 [C], bit g of word c says that channel c belongs to group g (bits >= G
+ *   are ignored); inv_scale2 DEVICE fp64 [C] = 1 / scale_c^2.  D2_g[a][b] = sum over c in g, ascending, of D2_c[a][b] * inv_scale2[c]
+ *   (each product rounded), Wv_g = sum over c in g of Wv_c, and the same five quantities follow; a group without a channel is NaN.
+ *   energy       [5][C][L_total] fp64: es, es_fair, skill, spread, Wv
+ *   energy_group [5][G][L_total] fp64: the same per group; NULL if and only if G == 0 (group_mask and inv_scale2 are then not read)
+ *   n_invalid    [C][L_total] int32: the invalid points
+ *   dist2        [C][L_total][M + 1][M + 1] fp64: D2, for diagnostics; NULL: not written
+ *   Columns l_off .. l_off + L - 1 are written, the others left alone.  No atomics: the fp64 additions run in an order that depends on
+ *   H, W and M only, so two runs give the same bits and a column's bits do not depend on C, L, L_total, l_off, the strides, G, the other
+ *   channels or dist2.
+ * workspace: ldc_rollout_energy_workspace_bytes(M, C, G, L, H, W) bytes of device scratch, 8-byte aligned (0 for arguments the call
+ *   refuses).  With NB = ceil((M + 1) / 4) it holds, per (channel, lead time), ceil(H W / 4096) + 1 records of NB (NB + 1) / 2 blocks
+ *   of 16 fp64 - the partial matrices of the point chunks and their total.  That term, 4 (M + 1)^2 bytes per record to leading order
+ *   (268 KiB at M = 256, 2.4 MB per (channel, lead time) on a 120 x 240 grid), is what bounds M at 256.
+ * LDC_ERR_ARG: a null or non-positive argument, G < 0, G > 0 without group_mask / inv_scale2 / energy_group, energy_group with G == 0,
+ * mean without std_, l_off + L > L_total or a workspace that is too small; LDC_ERR_UNSUPPORTED: M > 256, G > 32, C > 65535, L > 65535
+ * or H * W > 2^24; LDC_ERR_ALIGN: workspace, energy, energy_group, dist2 or inv_scale2 not 8-byte aligned.  Nothing is launched on an
+ * error. */
+long long ldc_rollout_energy_workspace_bytes(int M, int C, int G, int L, int H, int W);
+int ldc_rollout_energy(const float* forecast, long long member_stride, long long lead_stride, long long channel_stride, const float* mean,
+                       const float* std_, float target_std, const float* truth, long long truth_slot_stride,
+                       long long truth_channel_stride, const int* truth_slot, const float* lat_weight, const unsigned* group_mask,
+                       const double* inv_scale2, int G, int M, int C, int L, int H, int W, double* energy, double* energy_group,
+                       int* n_invalid, double* dist2, int L_total, int l_off, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Tropical-cyclone tracking through a decoded ensemble (track.hip).  Replaces the reference's tracker,

@@ -31,6 +31,11 @@ time: the smallest radius whose FSS reaches 0.5 + obs_fraction / 2, or -1), and 
 per decode batch, the additive sums pooled over the initial times (`regional_sums.npy` (R, C, lead time, 10), `regional_counts.npy`),
 `regional_bias.npy`, `regional_rmse.npy`, `regional_crps.npy`, ... (R, C, lead time) derived from the pooled sums, and `regions.json`;
 `--region_per_init` keeps the sums of every initial time too.
+`--energy` adds the energy score (`ldc_rollout_energy`, not in the reference): the multivariate generalisation of the CRPS over whole
+fields, per channel (`energy_score.npy`, `energy_score_fair.npy`, `energy_skill.npy`, `energy_spread.npy` (init time, C, lead time)
+float64, `energy_n_invalid.npy` int32) and, with `--energy_group NAME CHANNEL [CHANNEL ...]` (any number of times; implies `--energy`),
+per group of channels, each divided by its normalisation std (`energy_group_score.npy`, ... (init time, G, lead time)); `energy.json`
+names the groups, their channels and the scales.  The score is not additive over initial times: pool it by its mean over them.
 Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
 members and the reference's commented-out `single_mse` are out of scope.
 """
@@ -47,6 +52,7 @@ import numpy as np
 import torch
 
 from .track import LEVELS, NUM_ATM_VARS, VARIABLE_NAMES, mean_std_from_json
+from .energy import ENERGY_GROUP_NAMES, ENERGY_NAMES, EnergyGroup, _group_list, empty_energy, inverse_scale2, rollout_energy
 from .regional import (COUNT_NAMES, SUM_NAMES, REGIONAL_KEYS, REGIONAL_SCORE_NAMES, NAMED_REGIONS, Region, empty_regional, mask_words, region_mask as make_region_mask,
                        region_metadata, regional_scores, rollout_regional)
 from .utils import (MAX_FSS_SCALES, SCORE_NAMES, SPECTRUM_NAMES, Event, _radius_list, empty_events, empty_fss, empty_reliability, empty_spectrum, event_scores,
@@ -61,6 +67,9 @@ EVENTS_KEYS = ("event_hist", "event_hist_weighted", "event_n_invalid")  # what `
 FSS_KEYS = ("event_fss_sums", "event_fss_n_invalid")  # what `--fss_scales` adds to one initial time
 FSS_FILE_SCORES = dict(event_fss="fss", event_fss_target="fss_target", event_fss_obs_fraction="obs_fraction",
                        event_fss_freq_bias="freq_bias")  # <file>.npy: the score of `fss_scores`, from the pooled sums
+ENERGY_KEYS = ENERGY_NAMES + ("energy_n_invalid",)  # what `--energy` adds to one initial time; with groups also `ENERGY_GROUP_NAMES`
+ENERGY_FILE_KEYS = ENERGY_NAMES[:4] + ("energy_n_invalid",)  # <key>.npy; the weights stay with the scorer's result
+ENERGY_GROUP_FILE_KEYS = ENERGY_GROUP_NAMES[:4]
 EVENT_FILE_SCORES = ("brier", "bss", "reliability", "resolution", "uncertainty", "roc_area")  # event_<name>.npy, from the pooled histogram
 
 
@@ -121,7 +130,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                          total_num_steps: Optional[int] = None, crop_init: bool = False, force_ens_size: Optional[int] = None,
                          decode_batch_frames: Optional[int] = None, reliability: bool = False, spectrum: bool = False,
                          spectrum_row_weight: Optional[torch.Tensor] = None, events: Optional[Sequence] = None,
-                         regions: Optional[Sequence] = None, region_mask=None, fss_radii: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
+                         regions: Optional[Sequence] = None, region_mask=None, fss_radii: Optional[Sequence[int]] = None, energy: bool = False,
+                         energy_groups: Optional[Sequence] = None, energy_scales=None) -> Dict[str, torch.Tensor]:
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -156,7 +166,14 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     r (`regional.region_mask`; default: built from `regions` on `row_latitudes(H)` and the longitudes 0, 360 / W, ...); every decode
     batch also goes through one `ldc_rollout_regional` launch while it is on the device and the result gains `REGIONAL_KEYS`:
     `regional_sums` (R, C, total_num_steps, 10) float64 and `regional_counts` (R, C, total_num_steps, 3) int32 (`rollout_regional`;
-    columns past the last lead time are zeros).  Every other output is the bits of a call without it."""
+    columns past the last lead time are zeros).  Every other output is the bits of a call without it.
+
+    `energy`: every decode batch also goes through `ldc_rollout_energy` while it is on the device and the result gains `ENERGY_KEYS`:
+    `energy_score`, `energy_score_fair`, `energy_skill`, `energy_spread`, `energy_weight` (C, total_num_steps) float64 and
+    `energy_n_invalid` (C, total_num_steps) int32 (`rollout_energy`; columns past the last lead time are NaN).  `energy_groups`: a
+    sequence of `EnergyGroup(name, channels)` (implies `energy`); the result then gains `ENERGY_GROUP_NAMES` too, (G, total_num_steps)
+    float64.  `energy_scales` (C',), positive and finite, divides each channel of a group; default: `std_tensor`.  Up to 256 members;
+    the limits of the other scores stand.  Every other output is the bits of a call without it."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
 
@@ -193,6 +210,14 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             raise ValueError(f"{n_regions} regions: ldc_rollout_regional takes 1 .. 32 per call")
         if region_mask is None and isinstance(regions, (int, np.integer)):
             raise ValueError("a number of regions needs the region_mask")
+    energy = bool(energy) or bool(energy_groups)
+    if energy_scales is not None and not energy_groups:
+        raise ValueError("energy_scales needs energy_groups: the scales divide the channels of a group")
+    en_groups = None  # resolved against the decoded channel count at the first batch
+    if energy_groups:  # malformed groups and scales raise before anything is decoded; the channel range is checked at the first batch
+        _group_list(energy_groups, 1 << 31)
+        if energy_scales is not None:
+            inverse_scale2(energy_scales, torch.as_tensor(energy_scales).numel())
     dev = encdec_model.device
     if torch.device(dev).type != "cuda":
         raise RuntimeError("ladcast_amd scoring needs the model on the device (no CPU fallback)")
@@ -210,7 +235,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             raise ValueError("spectrum_row_weight must be non-negative (0 leaves a row out) and not NaN")
         spec_w = spec_w.to(dev, torch.float32)
     per = max(1, int(decode_batch_frames) // ens) if decode_batch_frames else 1  # lead times per decoder call: a lead time's members stay together
-    scores = rel = spec = evs = fss = reg = reg_words = None
+    scores = rel = spec = evs = fss = reg = reg_words = en = None
     for s0 in range(0, T, per):
         nl = min(per, T - s0)
         x = latents[:, :, s0 : s0 + nl].permute(2, 0, 1, 3, 4).reshape(nl * ens, C, h, w).contiguous()  # lead-major, then member
@@ -251,6 +276,15 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
             rollout_regional(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, reg_words, n_regions, clim=clim,
                              clim_slots=None if clim is None else c_slots[s0 : s0 + nl], lead_dim=0, mean=mean_d, std=std_d,
                              truth_slot=t_slots[s0 : s0 + nl], out=reg, l_off=s0)
+        if energy:
+            if en is None:
+                Cd = y.shape[1]
+                en_groups = _group_list(energy_groups, Cd)
+                if en_groups and energy_scales is None:
+                    energy_scales = std_tensor
+                en = empty_energy(ens, Cd, len(en_groups), total, dev)
+            rollout_energy(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, groups=en_groups, scales=energy_scales if en_groups else None,
+                           lead_dim=0, mean=mean_d, std=std_d, truth_slot=t_slots[s0 : s0 + nl], out=en, l_off=s0)
     host = scores.cpu()  # the one copy (and the one wait) of this initial time
     res = {k: host[i] for i, k in enumerate(SCORE_NAMES)}
     if reliability:
@@ -263,6 +297,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
         res.update({k: fss[k].cpu() for k in FSS_KEYS})
     if n_regions:
         res.update({k: reg[k].cpu() for k in REGIONAL_KEYS})
+    if energy:
+        res.update({k: en[k].cpu() for k in ENERGY_KEYS + (ENERGY_GROUP_NAMES if en_groups else ())})
     return res
 
 
@@ -409,6 +445,35 @@ def _gather_regional(regs: dict, res, time_str: str, total_num_steps: int, R: in
         regs["per_init"].append(s)
 
 
+def _gather_energy(en: dict, res, time_str: str, total_num_steps: int, G: int) -> None:
+    """one initial time's `ENERGY_FILE_KEYS` (and with groups `ENERGY_GROUP_FILE_KEYS`) into the run's: kept per initial time, float64
+    (`energy_n_invalid`: int32) - the score is not additive over initial times"""
+    keys = ENERGY_FILE_KEYS + (ENERGY_GROUP_FILE_KEYS if G else ())
+    missing = [k for k in keys if k not in res]
+    if missing:
+        raise ValueError(f"{time_str}: --energy needs {missing} from the scorer")
+    a = {k: np.asarray(res[k]) for k in keys}
+    C = a["energy_score"].shape[0]
+    if any(a[k].shape != (C, total_num_steps) for k in ENERGY_FILE_KEYS) or any(a[k].shape != (G, total_num_steps) for k in keys[len(ENERGY_FILE_KEYS):]):
+        raise ValueError(f"{time_str}: energy arrays of shapes { {k: v.shape for k, v in a.items()} }, expected (C, {total_num_steps}) and "
+                         f"({G}, {total_num_steps})")
+    for k in keys:
+        en.setdefault(k, []).append(a[k].astype(np.int32 if k == "energy_n_invalid" else np.float64))
+
+
+def parse_energy_groups(entries: Sequence[Sequence[str]], names: Sequence[str]) -> List[EnergyGroup]:
+    """`--energy_group NAME CHANNEL [CHANNEL ...]` entries -> the `EnergyGroup` list; CHANNEL is a name of `names` or an index, resolved
+    as `--event` resolves it"""
+    from .products import resolve_channels
+
+    groups = []
+    for entry in entries:
+        if len(entry) < 2:
+            raise ValueError(f"--energy_group {' '.join(entry)}: a name and at least one channel are needed")
+        groups.append(EnergyGroup(entry[0], tuple(resolve_channels(list(entry[1:]), names))))
+    return _group_list(groups, len(names))
+
+
 def parse_regions(region: Sequence[str], region_box: Sequence[Sequence[str]], region_surface: Sequence[Sequence[str]]) -> List[Region]:
     """`--region NAME`, `--region_box NAME LAT0 LAT1 LON0 LON1` and `--region_surface NAME land|sea` entries -> the `Region` list, named
     regions first; a surface applies to the region of that name"""
@@ -512,6 +577,14 @@ def main(argv=None, score: Optional[Callable] = None):
     each region).  `--region_per_init` also writes `regional_sums_per_init.npy` (init time, R, C, lead time, 10): off by default, at a
     year of initial times, 84 channels and 13 regions it runs to gigabytes.  Without the flags the launches and files are unchanged.
 
+    `--energy` (the scorer then returns `ENERGY_KEYS` too) adds `energy_score.npy`, `energy_score_fair.npy`, `energy_skill.npy`,
+    `energy_spread.npy` (init time, C, lead time) float64 and `energy_n_invalid.npy` int32; `--energy_group NAME CHANNEL [CHANNEL ...]`
+    (any number of times, CHANNEL resolved as `--event` resolves it; implies `--energy`; the scorer then returns `ENERGY_GROUP_NAMES`
+    too) adds `energy_group_score.npy`, `energy_group_score_fair.npy`, `energy_group_skill.npy`, `energy_group_spread.npy` (init time, G,
+    lead time) float64, every channel of a group divided by its normalisation std; `energy.json` holds the group names, channels and
+    scales.  The energy score is not additive over initial times: the pooled value is the mean over the first axis, taken by the
+    reader.  Without the flags the launches and files are unchanged.
+
     `timestamp.npy` is float32, as the reference stores it: YYYYMMDDHH does not fit fp32's 24 bits, e.g. 2018123118 reads back as
     2018123136.  The per-time file names carry the exact time."""
     ap = argparse.ArgumentParser(description="Score saved ensemble rollouts (evaluate_ens_gpu.py on .npy data)")
@@ -550,6 +623,9 @@ def main(argv=None, score: Optional[Callable] = None):
                     help="restrict the region NAME to land or sea points (needs --land_sea_mask_path)")
     ap.add_argument("--land_sea_mask_path", type=str, default=None, help=".npy (H_in, W): land where >= 0.5")
     ap.add_argument("--region_per_init", action="store_true", help="also write regional_sums_per_init.npy (init time, R, C, lead time, 10)")
+    ap.add_argument("--energy", action="store_true", help="also write the energy score per channel: energy_score, energy_score_fair, energy_skill, energy_spread, energy_n_invalid")
+    ap.add_argument("--energy_group", nargs="+", action="append", default=[], metavar="NAME_THEN_CHANNELS",
+                    help="NAME CHANNEL [CHANNEL ...]: also score these channels together, each divided by its normalisation std; may be given several times; implies --energy")
     ap.add_argument("--levels", type=int, nargs="+", default=LEVELS, help="pressure levels of the atmospheric variables, in channel order (--event channel names)")
     ap.add_argument("--num_atm_vars", type=int, default=NUM_ATM_VARS, help="leading variables that have one channel per level (--event channel names)")
     args = ap.parse_args(argv)
@@ -579,6 +655,15 @@ def main(argv=None, score: Optional[Callable] = None):
         fss_radii = parse_fss_scales(args.fss_scales)
     grid_w = None  # points per row, where the data tell it
 
+    energy_groups, energy_names = [], None
+    if args.energy_group:
+        from .validate_AR import column_names
+
+        energy_names = column_names(args.variable_names, args.levels, args.num_atm_vars)
+        energy_groups = parse_energy_groups(args.energy_group, energy_names)
+    want_energy = args.energy or bool(energy_groups)
+    energy_scales = None
+
     regions = parse_regions(args.region, args.region_box, args.region_surface)
     if any(r.surface for r in regions) and args.land_sea_mask_path is None:
         raise ValueError("--region_surface needs --land_sea_mask_path")
@@ -601,6 +686,8 @@ def main(argv=None, score: Optional[Callable] = None):
             raise SystemExit("--encdec_model, --data_path and --climatology_path are required")
         with open(args.normalization_json) as f:
             mean_t, std_t = mean_std_from_json(json.load(f), args.variable_names)
+        if energy_groups:
+            energy_scales = [float(v) for v in torch.as_tensor(std_t).reshape(-1).tolist()]
         model = _load_encdec(args.encdec_model).to("cuda").eval()
         model.set_gemm_precision(args.gemm_precision)
         shape = np.load(files[0][1], mmap_mode="r").shape
@@ -626,7 +713,7 @@ def main(argv=None, score: Optional[Callable] = None):
                                         total_num_steps=total_num_steps, crop_init=args.crop_init, force_ens_size=args.force_ens_size,
                                         decode_batch_frames=args.decode_batch_frames, reliability=args.reliability, spectrum=args.spectrum,
                                         spectrum_row_weight=spec_w, events=events or None, regions=regions or None, region_mask=reg_mask,
-                                        fss_radii=fss_radii)
+                                        fss_radii=fss_radii, energy=want_energy, energy_groups=energy_groups or None)
 
     os.makedirs(args.output, exist_ok=True)
     gathered = {k: [] for k in SCORE_NAMES}
@@ -635,6 +722,7 @@ def main(argv=None, score: Optional[Callable] = None):
     evs = dict(event_n_invalid=[], event_hist=None, event_hist_weighted=None)
     fss = dict(event_fss_sums=None, event_fss_n_invalid=[])
     regs = dict(regional_sums=None, regional_counts=None, per_init=[])
+    engy: dict = {}
     for i, (time_str, path) in enumerate(files):
         print(f"processing time_str: {time_str}, remaining: {len(files) - i - 1}")
         init = _to_datetime(int(time_str))
@@ -656,6 +744,8 @@ def main(argv=None, score: Optional[Callable] = None):
             _gather_fss(fss, res, time_str, total_num_steps, len(events), len(fss_radii))
         if regions:
             _gather_regional(regs, res, time_str, total_num_steps, len(regions), args.region_per_init)
+        if want_energy:
+            _gather_energy(engy, res, time_str, total_num_steps, len(energy_groups))
     out = {k: np.stack(v) for k, v in gathered.items()}
     if args.reliability:
         out.update({k: np.stack(rel[k]) for k in ("ens_var", "ssr", "n_invalid")}, rank_hist=rel["rank_hist"], rank_hist_weighted=rel["rank_hist_weighted"])
@@ -687,6 +777,13 @@ def main(argv=None, score: Optional[Callable] = None):
                                  n_points=None, weight=None) for r in regions]
         with open(os.path.join(args.output, "regions.json"), "w") as f:
             json.dump(dict(regions=regions_meta, members=ens, sums=list(SUM_NAMES), counts=list(COUNT_NAMES)), f, indent=1)
+    if want_energy:
+        out.update({k: np.stack(v) for k, v in engy.items()})
+        with open(os.path.join(args.output, "energy.json"), "w") as f:
+            json.dump(dict(groups=[dict(name=g.name, channels=list(g.channels),
+                                        channel_names=None if energy_names is None else [energy_names[c] for c in g.channels],
+                                        scales=None if energy_scales is None else [energy_scales[c] for c in g.channels]) for g in energy_groups]),
+                      f, indent=1)
     out["timestamp"] = np.array([int(t) for t, _ in files]).astype(np.float32)  # as the reference: a float32 tensor of YYYYMMDDHH
     for k, a in out.items():
         np.save(os.path.join(args.output, f"{k}.npy"), a)

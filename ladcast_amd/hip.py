@@ -141,6 +141,8 @@ def _load():
         "ldc_rollout_fss": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, POINTER(EventsDesc), POINTER(c_int), I, P, P, I, I, P, L, P]),
         "ldc_rollout_regional_workspace_bytes": (L, [I, I, I, I, I, I]),
         "ldc_rollout_regional": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, P, I, I, I, I, I, I, P, P, I, I, P, L, P]),
+        "ldc_rollout_energy_workspace_bytes": (L, [I, I, I, I, I, I]),
+        "ldc_rollout_energy": (I, [P, L, L, L, P, P, F, P, L, L, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, L, P]),
         "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
         "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
         "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
@@ -422,7 +424,7 @@ def ensemble_scores(forecast, truth, clim, lat_weight, out, *, M, C, H, W, membe
 
 
 def _forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std):
-    """the leading arguments of ldc_rollout_scores / _reliability / _spectrum / _products / _events / _regional and ldc_validation_scores"""
+    """the leading arguments of ldc_rollout_scores / _reliability / _spectrum / _products / _events / _regional / _energy and ldc_validation_scores"""
     return _p(forecast), member_stride, lead_stride, channel_stride, _p(mean), _p(std), float(target_std)
 
 
@@ -589,6 +591,25 @@ def rollout_regional(forecast, truth, truth_slot, clim, clim_slot, lat_weight, r
                                     *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
                                     clim_channel_stride, _p(clim_slot), _p(lat_weight), _p(region_mask), R, M, C, L, H, W, _p(sums), _p(counts),
                                     L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_regional")
+
+
+ENERGY_MAX_MEMBERS, ENERGY_MAX_GROUPS, ENERGY_PLANES = 256, 32, 5  # the limits of ldc_rollout_energy and the planes of its score buffers
+
+
+def rollout_energy(forecast, truth, truth_slot, lat_weight, energy, n_invalid, *, M, C, L, H, W, member_stride, lead_stride, channel_stride,
+                   truth_slot_stride, truth_channel_stride, group_mask=None, inv_scale2=None, G=0, energy_group=None, dist2=None, mean=None,
+                   std=None, target_std=1.0, L_total, l_off=0):
+    """energy (fp64) [5][C][L_total] = es, es_fair, skill, spread, Wv; energy_group (fp64) [5][G][L_total] (None iff G == 0); n_invalid
+    (int32) [C][L_total]; dist2 (fp64) [C][L_total][M + 1][M + 1] or None: columns l_off .. l_off + L - 1 of L lead times in one call
+    (ladcast_hip.h: ldc_rollout_energy); group_mask: device int32 / uint32 words [C], bit g = group g; inv_scale2: device fp64 [C];
+    truth_slot: device int32 [L]"""
+    _dev(forecast, truth, truth_slot, lat_weight, group_mask, inv_scale2, energy, energy_group, n_invalid, dist2, mean, std)
+    nbytes = int(lib.ldc_rollout_energy_workspace_bytes(M, C, G, L, H, W))
+    ws = _workspace("rollout_energy", forecast.device, max(nbytes, 8), grow=True)
+    _check(lib.ldc_rollout_energy(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                  *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(lat_weight), _p(group_mask),
+                                  _p(inv_scale2), G, M, C, L, H, W, _p(energy), _p(energy_group), _p(n_invalid), _p(dist2), L_total, l_off,
+                                  _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_energy")
 
 
 def recon_preprocess(x, mean, std, out, nan_mask=None, *, B, C, H, W, batch_stride, channel_stride, row_stride, sst_channel=-1):
