@@ -17,7 +17,7 @@ from typing import Dict, NamedTuple, Optional, Sequence
 import torch
 
 from .. import hip
-from .utils import _channel_affine, _forecast_view, _plane_table, _row_weight, _upload_slots
+from .utils import _Buf, _empty, _launch_args, _out_buffers, _prologue
 
 MAX_ENERGY_MEMBERS, MAX_ENERGY_GROUPS = hip.ENERGY_MAX_MEMBERS, hip.ENERGY_MAX_GROUPS
 ENERGY_NAMES = ("energy_score", "energy_score_fair", "energy_skill", "energy_spread", "energy_weight")  # the planes of `energy`, in order
@@ -82,6 +82,10 @@ class EnergyDict(dict):
     int32; with groups energy_group_score, ... : (G, L_total) float64; when asked energy_dist2: (C, L_total, M + 1, M + 1) float64} over
     the device buffers `ldc_rollout_energy` fills"""
 
+    _spec = (_Buf(lambda Lt, M, C, G, dist2: (hip.ENERGY_PLANES, C, Lt), torch.float64, float("nan"), 2), _Buf(lambda Lt, M, C, G, dist2: (C, Lt), torch.int32, 0, 1),
+             _Buf(lambda Lt, M, C, G, dist2: (hip.ENERGY_PLANES, G, Lt) if G else None, torch.float64, float("nan"), 2, "none"),
+             _Buf(lambda Lt, M, C, G, dist2: (C, Lt, M + 1, M + 1) if dist2 else None, torch.float64, float("nan"), 1, "none"))
+
     def __init__(self, energy, n_invalid, energy_group=None, dist2=None):
         super().__init__({k: energy[i] for i, k in enumerate(ENERGY_NAMES)})
         self["energy_n_invalid"] = n_invalid
@@ -94,9 +98,7 @@ class EnergyDict(dict):
 
 def empty_energy(M: int, C: int, G: int, L_total: int, device, dist2: bool = False) -> EnergyDict:
     """the result of `rollout_energy` before any column is written: scores NaN, weights NaN, `energy_n_invalid` zero, `energy_dist2` NaN"""
-    nan = lambda *shape: torch.full(shape, float("nan"), device=device, dtype=torch.float64)  # noqa: E731
-    return EnergyDict(nan(hip.ENERGY_PLANES, C, L_total), torch.zeros(C, L_total, device=device, dtype=torch.int32),
-                      nan(hip.ENERGY_PLANES, G, L_total) if G else None, nan(C, L_total, M + 1, M + 1) if dist2 else None)
+    return EnergyDict(*_empty(EnergyDict._spec, L_total, device, M=M, C=C, G=G, dist2=dist2))
 
 
 @torch.no_grad()
@@ -122,13 +124,9 @@ def rollout_energy(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torc
     forecast, `lead_dim`, `mean` / `std` / `target_std`, truth / `truth_slot`, `out` / `l_off`: as `rollout_regional`.  Returns an
     `EnergyDict` of float64 device tensors with L_total = l_off + L columns (unwritten columns: NaN), or fills columns
     l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_energy`) returned for the same M, C, groups and `return_dist2`."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    if not 1 <= M <= MAX_ENERGY_MEMBERS:
-        raise ValueError(f"{M} members: ldc_rollout_energy serves 1 .. {MAX_ENERGY_MEMBERS}")
-    dev = f.device
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    w = _row_weight(lat_weight, H, dev, "lat_weight")
-    mn, sd = _channel_affine(mean, std, C, dev)
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slot), weight=(lat_weight, "lat_weight"),
+                  members=("ldc_rollout_energy", MAX_ENERGY_MEMBERS))
+    C, dev = r.C, r.f.device
     grs = _group_list(groups, C)
     G = len(grs)
     if G and scales is None:
@@ -136,28 +134,13 @@ def rollout_energy(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torc
     inv_s2 = None if scales is None else inverse_scale2(scales, C)
     if l_off < 0:
         raise ValueError("l_off must not be negative")
-    bufs = None
-    if out is not None:
-        bufs = getattr(out, "_buffers", None)
-        ok = bufs is not None and len(bufs) == 4 and bufs[0] is not None and bufs[0].dim() == 3 and \
-            all(b is None or (b.is_contiguous() and b.device == dev) for b in bufs)
-        if ok:
-            Lt = bufs[0].shape[2]
-            ok = l_off + L <= Lt and tuple(bufs[0].shape) == (hip.ENERGY_PLANES, C, Lt) and bufs[0].dtype == torch.float64 \
-                and bufs[1] is not None and tuple(bufs[1].shape) == (C, Lt) and bufs[1].dtype == torch.int32 \
-                and (bufs[2] is None) == (G == 0) and (G == 0 or (tuple(bufs[2].shape) == (hip.ENERGY_PLANES, G, Lt) and bufs[2].dtype == torch.float64)) \
-                and (bufs[3] is None) == (not return_dist2) \
-                and (bufs[3] is None or (tuple(bufs[3].shape) == (C, Lt, M + 1, M + 1) and bufs[3].dtype == torch.float64))
-        if not ok:
-            raise ValueError("out must be the dict an earlier rollout_energy call (or empty_energy) returned for the same ensemble size, "
-                             "channels, number of groups and return_dist2, with room for columns l_off .. l_off + L - 1")
+    bufs = _out_buffers(EnergyDict._spec, out, r, l_off, M=r.M, C=C, G=G, dist2=return_dist2, msg=(
+        "out must be the dict an earlier rollout_energy call (or empty_energy) returned for the same ensemble size, "
+        "channels, number of groups and return_dist2, with room for columns l_off .. l_off + L - 1"))
     hip._dev(forecast, truth, lat_weight, mean, std)
-    if bufs is None:
-        bufs = empty_energy(M, C, G, l_off + L, dev, dist2=return_dist2)._buffers
-    slots = _upload_slots(t_slots, dev)
+    bufs = bufs or _empty(EnergyDict._spec, l_off + r.L, dev, M=r.M, C=C, G=G, dist2=return_dist2)
+    args, kw = _launch_args(r, bufs[0].shape[2], l_off)
     words = hip.upload_nonblocking(group_words(grs, C), dev) if G else None
     inv_d = hip.upload_nonblocking(inv_s2.contiguous(), dev) if G else None
-    hip.rollout_energy(f, t, slots, w, bufs[0], bufs[1], M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
-                       channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, group_mask=words, inv_scale2=inv_d, G=G,
-                       energy_group=bufs[2], dist2=bufs[3], mean=mn, std=sd, target_std=target_std, L_total=bufs[0].shape[2], l_off=l_off)
+    hip.rollout_energy(*args, bufs[0], bufs[1], group_mask=words, inv_scale2=inv_d, G=G, energy_group=bufs[2], dist2=bufs[3], **kw)
     return EnergyDict(*bufs)

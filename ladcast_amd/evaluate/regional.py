@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from .utils import _channel_affine, _forecast_view, _plane_table, _row_weight, _upload_slots
+from .utils import _Buf, _empty, _launch_args, _out_buffers, _prologue
 
 MAX_REGIONS, MAX_REGIONAL_MEMBERS = hip.REGIONS_MAX, hip.REGIONAL_MAX_MEMBERS
 N_SUMS, N_COUNTS = hip.REGIONAL_SUMS, hip.REGIONAL_COUNTS
@@ -147,6 +147,8 @@ class RegionalDict(dict):
     """{regional_sums: (R, C, L_total, 10) fp64; regional_counts: (R, C, L_total, 3) int32} over the two device buffers
     `ldc_rollout_regional` fills (`SUM_NAMES`, `COUNT_NAMES`)"""
 
+    _spec = (_Buf(lambda Lt, R, C: (R, C, Lt, N_SUMS), torch.float64, 0, 2), _Buf(lambda Lt, R, C: (R, C, Lt, N_COUNTS), torch.int32, 0, 2))
+
     def __init__(self, sums, counts):
         super().__init__(regional_sums=sums, regional_counts=counts)
         self._buffers = (sums, counts)
@@ -154,8 +156,7 @@ class RegionalDict(dict):
 
 def empty_regional(R: int, C: int, L_total: int, device) -> RegionalDict:
     """the result of `rollout_regional` before any column is written: all sums and counts zero"""
-    return RegionalDict(torch.zeros(R, C, L_total, N_SUMS, device=device, dtype=torch.float64),
-                        torch.zeros(R, C, L_total, N_COUNTS, device=device, dtype=torch.int32))
+    return RegionalDict(*_empty(RegionalDict._spec, L_total, device, R=R, C=C))
 
 
 def mask_words(mask, H: int, W: int) -> torch.Tensor:
@@ -189,14 +190,9 @@ def rollout_regional(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: to
     forecast, `lead_dim`, `mean` / `std` / `target_std`, truth / `truth_slot`, `clim` / `clim_slots`, `out` / `l_off`: as
     `rollout_events`.  Returns a `RegionalDict` of device tensors with L_total = l_off + L columns (unwritten columns: zeros), or fills
     columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_regional`) returned for the same R and C."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    if not 1 <= M <= MAX_REGIONAL_MEMBERS:
-        raise ValueError(f"{M} members: ldc_rollout_regional serves 1 .. {MAX_REGIONAL_MEMBERS}")
-    dev = f.device
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
-    w = _row_weight(lat_weight, H, dev, "lat_weight")
-    mn, sd = _channel_affine(mean, std, C, dev)
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slot), clim=(clim, clim_slots), weight=(lat_weight, "lat_weight"),
+                  members=("ldc_rollout_regional", MAX_REGIONAL_MEMBERS))
+    H, W, dev = r.H, r.W, r.f.device
     R = int(n_regions)
     if not 1 <= R <= MAX_REGIONS:
         raise ValueError(f"{R} regions: ldc_rollout_regional takes 1 .. {MAX_REGIONS} per call")
@@ -208,25 +204,13 @@ def rollout_regional(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: to
         words = mask_words(region_mask, H, W)
     if l_off < 0:
         raise ValueError("l_off must not be negative")
-    bufs = None
-    if out is not None:
-        bufs = getattr(out, "_buffers", None)
-        ok = bufs is not None and len(bufs) == 2 and bufs[0].dim() == 4 and all(b.is_contiguous() and b.device == dev for b in bufs)
-        if ok:
-            Lt = bufs[0].shape[2]
-            ok = l_off + L <= Lt and tuple(bufs[0].shape) == (R, C, Lt, N_SUMS) and tuple(bufs[1].shape) == (R, C, Lt, N_COUNTS) \
-                and bufs[0].dtype == torch.float64 and bufs[1].dtype == torch.int32
-        if not ok:
-            raise ValueError("out must be the dict an earlier rollout_regional call (or empty_regional) returned for the same number of regions "
-                             "and channels, with room for columns l_off .. l_off + L - 1")
+    bufs = _out_buffers(RegionalDict._spec, out, r, l_off, R=R, C=r.C, msg=(
+        "out must be the dict an earlier rollout_regional call (or empty_regional) returned for the same number of regions "
+        "and channels, with room for columns l_off .. l_off + L - 1"))
     hip._dev(forecast, truth, clim, lat_weight, mean, std)
-    if bufs is None:
-        bufs = empty_regional(R, C, l_off + L, dev)._buffers
+    bufs = bufs or _empty(RegionalDict._spec, l_off + r.L, dev, R=R, C=r.C)
     if not words.is_cuda:
         words = hip.upload_nonblocking(words, dev)
-    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], dev)
-    hip.rollout_regional(f, t, slots[0], c, None if c is None else slots[1], w, words, *bufs, R=R, M=M, C=C, L=L, H=H, W=W,
-                         member_stride=f.stride(0), lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss,
-                         truth_channel_stride=t_cs, clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mn, std=sd, target_std=target_std,
-                         L_total=bufs[0].shape[2], l_off=l_off)
+    args, kw = _launch_args(r, bufs[0].shape[2], l_off)
+    hip.rollout_regional(*args, words, *bufs, R=R, **kw)
     return RegionalDict(*bufs)

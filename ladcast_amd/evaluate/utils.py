@@ -2,7 +2,8 @@
 ladcast/evaluate/evaluate_ens_gpu.py:339-425).  Same function names and argument meaning; the forecast is read once by
 one fused HIP kernel (`ldc_ensemble_scores`) instead of ~40 torch ops.  Tensors must live on a HIP device: there is no
 CPU path."""
-from typing import Dict, NamedTuple, Optional
+from collections import namedtuple
+from typing import Callable, Dict, NamedTuple, Optional
 
 import torch
 
@@ -131,8 +132,8 @@ def _plane_table(t: torch.Tensor, slots, C: int, L: int, H: int, W: int, what: s
     return t, t.stride(0), t.stride(1), slots
 
 
-# What the five rollout_* / validation_scores wrappers below share.  Each wrapper runs every check that needs no device first (ValueError,
-# NotImplementedError), then asks for the device (`hip._dev`) with the tensors it cannot take from the host, then allocates and launches.
+# What the nine rollout_* / validation_scores wrappers (here, in regional.py and energy.py) share.  Each runs every check that needs no device first
+# (ValueError, NotImplementedError): `_prologue`, its own limits, `l_off`, `out`; then `hip._dev` on the tensors it cannot take from the host.
 def _forecast_view(forecast: torch.Tensor, lead_dim: int):
     """-> (f, M, C, L, H, W): the forecast as (ens, C, L, H, W) with a contiguous (H, W) plane, any member / lead / channel strides"""
     if forecast.dim() != 5 or lead_dim not in (0, 2):
@@ -156,26 +157,82 @@ def _channel_affine(mean, std, C: int, dev):
     return mean.to(dev, torch.float32).reshape(-1).contiguous(), std.to(dev, torch.float32).reshape(-1).contiguous()
 
 
-def _row_weight(w: torch.Tensor, H: int, dev, what: str) -> torch.Tensor:
-    """`lat_weight` / `row_weight` -> a contiguous fp32 (H,) vector on `dev`"""
-    if w.numel() != H:
-        raise ValueError(f"{what} must have one value per latitude row")
-    return w.to(dev, torch.float32).reshape(-1).contiguous()
-
-
 def _upload_slots(slots, dev) -> torch.Tensor:
     """a host list of ints (or a list of such lists) -> an int32 device tensor, without stalling the host"""
     return hip.upload_nonblocking(torch.tensor(slots, dtype=torch.int32), dev)
 
 
-def _score_buffer(out, n: int, C: int, dev, who: str):
-    """the contiguous (n, C, L_total) fp32 buffer behind `out`, the dict an earlier call of `who` returned; None when there is no `out`"""
+# What `_prologue` found: the forecast view and its sizes; truth / clim as `_plane_table` gives them - None: the wrapper takes none,
+# (None, 0, 0, None): it takes a climatology and none was given; the row weight and the channel affine on the device.
+_Rollout = namedtuple("_Rollout", "f M C L H W truth clim w mn sd target_std")
+
+
+def _launch_args(r: _Rollout, L_total: int, l_off: int):
+    """After `hip._dev`: the slots go up in one upload.  -> (the device tensors a `hip.rollout_*` binding begins with, its common keywords)"""
+    f = r.f
+    kw = dict(M=r.M, C=r.C, L=r.L, H=r.H, W=r.W, member_stride=f.stride(0), lead_stride=f.stride(2), channel_stride=f.stride(1),
+              mean=r.mn, std=r.sd, target_std=r.target_std, L_total=L_total, l_off=l_off)
+    if r.truth is None:
+        return (f,), kw
+    t, kw["truth_slot_stride"], kw["truth_channel_stride"], t_slots = r.truth
+    if r.clim is None:
+        return (f, t, _upload_slots(t_slots, f.device), r.w), kw
+    c, kw["clim_slot_stride"], kw["clim_channel_stride"], c_slots = r.clim
+    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], f.device)
+    return (f, t, slots[0], c, None if c is None else slots[1], r.w), kw
+
+
+def _prologue(forecast, lead_dim: int, mean, std, target_std: float, *, truth=None, clim=None, weight=None, members=None) -> _Rollout:
+    """What every wrapper does before its own checks, in one order: the forecast view (its errors win), the ensemble size, the truth
+    table, the climatology table, the row weight, the channel affine.  truth: (tensor, slots); clim: (tensor or None, slots), or None for
+    a wrapper without a climatology argument; weight: (tensor, its name in error messages); members: (the entry point, its largest M)."""
+    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
+    if members is not None and not 1 <= M <= members[1]:
+        raise ValueError(f"{M} members: {members[0]} serves 1 .. {members[1]}")
+    t = None if truth is None else _plane_table(*truth, C, L, H, W, "truth")
+    c = clim if clim is None else (None, 0, 0, None) if clim[0] is None else _plane_table(*clim, C, L, H, W, "clim")
+    if weight is not None and weight[0].numel() != H:
+        raise ValueError(f"{weight[1]} must have one value per latitude row")
+    w = None if weight is None else weight[0].to(f.device, torch.float32).reshape(-1).contiguous()
+    return _Rollout(f, M, C, L, H, W, t, c, w, *_channel_affine(mean, std, C, f.device), target_std)
+
+
+class _Buf(NamedTuple):
+    """One device buffer of a result type, stated once in the type's `_spec`: `_empty` builds it and `_out_buffers` holds an `out` to it."""
+
+    shape: Callable  # (L_total, **the type's sizes) -> the shape; None: this call does not ask for the buffer
+    dtype: torch.dtype
+    fill: float  # of the columns no call has written
+    lead: int  # the axis of length L_total
+    unasked: str = ""  # an optional buffer the call does not ask for: "none" - it must be None; "kept" - it is left alone
+
+
+def _empty(spec, L_total: int, device, **sizes) -> tuple:
+    """the buffers of `spec` before any column is written"""
+    shapes = [b.shape(L_total, **sizes) for b in spec]
+    return tuple(None if s is None else torch.full(s, b.fill, device=device, dtype=b.dtype) for b, s in zip(spec, shapes))
+
+
+def _out_buffers(spec, out, r: _Rollout, l_off: int, msg: str, room: bool = True, **sizes):
+    """the buffers behind a wrapper's `out` (None without one), held to `spec`: their count, None-ness, shape, dtype, contiguity, device
+    and (`room`) columns l_off .. l_off + L - 1; ValueError(msg) otherwise"""
     if out is None:
         return None
-    buf = getattr(out, "_buffer", None) if not isinstance(out, torch.Tensor) else out
-    if buf is None or buf.dim() != 3 or buf.shape[:2] != (n, C) or not buf.is_contiguous() or buf.dtype != torch.float32 or buf.device != dev:
-        raise ValueError(f"out must be the dict an earlier {who} call returned (or its contiguous ({n}, C, L_total) fp32 buffer)")
-    return buf
+    bufs = out if isinstance(out, tuple) else getattr(out, "_buffers", None)
+    ok = bufs is not None and len(bufs) == len(spec)
+    if ok:
+        asked = [b.shape(0, **sizes) is not None for b in spec]
+        Lt = next((t.shape[b.lead] for b, t, a in zip(spec, bufs, asked) if a and isinstance(t, torch.Tensor) and t.dim() > b.lead), None)
+        ok = Lt is not None and (not room or l_off + r.L <= Lt)
+        for b, t, a in zip(spec, bufs, asked):
+            if a:
+                ok = ok and isinstance(t, torch.Tensor) and tuple(t.shape) == b.shape(Lt, **sizes) and t.dtype == b.dtype and t.is_contiguous() \
+                    and t.device == r.f.device
+            elif b.unasked == "none":
+                ok = ok and t is None
+    if not ok:
+        raise ValueError(msg)
+    return tuple(bufs)
 
 
 @torch.no_grad()
@@ -194,30 +251,34 @@ def rollout_scores(forecast: torch.Tensor, truth: torch.Tensor, clim: Optional[t
     climatology); clim None = no ACC; they are never transformed.  Returns the dict of five (C, L_total) device tensors under
     `ensemble_scores`' names: a fresh one (L_total = lead_offset + L, unwritten columns NaN), or `out` - the dict an earlier call
     returned - of which columns lead_offset .. lead_offset + L - 1 are written."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    dev = f.device
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slots, C, L, H, W, "truth")
-    c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
-    w = _row_weight(lat_weight, H, dev, "lat_weight")
-    mn, sd = _channel_affine(mean, std, C, dev)
-    buf = _score_buffer(out, len(SCORE_NAMES), C, dev, "rollout_scores")
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slots), clim=(clim, clim_slots), weight=(lat_weight, "lat_weight"))
+    buf = _score_buffer(out, SCORE_NAMES, r, lead_offset, "rollout_scores")
     hip._dev(forecast, truth, clim, lat_weight, mean, std)
     if buf is None:
-        buf = torch.full((len(SCORE_NAMES), C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
-    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], dev)
-    hip.rollout_scores(f, t, slots[0], c, None if c is None else slots[1], w, buf, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0),
-                       lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs,
-                       clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mn, std=sd, target_std=target_std, nan_channel=sst_channel,
-                       L_total=buf.shape[2], l_off=lead_offset)
+        buf, = _empty(ScoreDict._spec, lead_offset + r.L, r.f.device, n=len(SCORE_NAMES), C=r.C)
+    args, kw = _launch_args(r, buf.shape[2], lead_offset)
+    hip.rollout_scores(*args, buf, nan_channel=sst_channel, **kw)
     return ScoreDict(buf)
 
 
 class ScoreDict(dict):
     """{name: (C, L_total) view} over one contiguous (len(names), C, L_total) device buffer: the arrays travel to the host in one copy"""
 
+    _spec = (_Buf(lambda Lt, n, C: (n, C, Lt), torch.float32, float("nan"), 2),)
+
     def __init__(self, buf: torch.Tensor, names=SCORE_NAMES):
         super().__init__({k: buf[i] for i, k in enumerate(names)})
         self._buffer = buf
+
+
+def _score_buffer(out, names, r: _Rollout, l_off: int, who: str):
+    """the buffer behind `out`, the dict an earlier call of `who` returned, or that buffer itself; None when there is no `out`.  Room for the
+    columns is left to the library, which refuses and writes nothing"""
+    if out is None:
+        return None
+    buf = out if isinstance(out, torch.Tensor) else getattr(out, "_buffer", None)
+    msg = f"out must be the dict an earlier {who} call returned (or its contiguous ({len(names)}, C, L_total) fp32 buffer)"
+    return _out_buffers(ScoreDict._spec, (buf,), r, l_off, msg, room=False, n=len(names), C=r.C)[0]
 
 
 VALIDATION_SCORE_NAMES = ("ens_mse", "single_mse", "crps")  # the planes of ldc_validation_scores' `out`, in order
@@ -235,19 +296,13 @@ def validation_scores(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: t
     forecast, `lead_dim`, `mean` / `std` / `target_std`, truth / `truth_slots`, `out` / `lead_offset`: as `rollout_scores`.  Returns the
     dict of three (C, L_total) device tensors over one contiguous (3, C, L_total) buffer (`VALIDATION_SCORE_NAMES`); unwritten columns of
     a fresh one are NaN."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    dev = f.device
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slots, C, L, H, W, "truth")
-    w = _row_weight(lat_weight, H, dev, "lat_weight")
-    mn, sd = _channel_affine(mean, std, C, dev)
-    buf = _score_buffer(out, len(VALIDATION_SCORE_NAMES), C, dev, "validation_scores")
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slots), weight=(lat_weight, "lat_weight"))
+    buf = _score_buffer(out, VALIDATION_SCORE_NAMES, r, lead_offset, "validation_scores")
     hip._dev(forecast, truth, lat_weight, mean, std)
     if buf is None:
-        buf = torch.full((len(VALIDATION_SCORE_NAMES), C, lead_offset + L), float("nan"), device=dev, dtype=torch.float32)
-    slots = _upload_slots(t_slots, dev)
-    hip.validation_scores(f, t, slots, w, buf, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
-                          channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mn, std=sd,
-                          target_std=target_std, L_total=buf.shape[2], l_off=lead_offset)
+        buf, = _empty(ScoreDict._spec, lead_offset + r.L, r.f.device, n=len(VALIDATION_SCORE_NAMES), C=r.C)
+    args, kw = _launch_args(r, buf.shape[2], lead_offset)
+    hip.validation_scores(*args, buf, **kw)
     return ScoreDict(buf, VALIDATION_SCORE_NAMES)
 
 
@@ -259,6 +314,9 @@ class ReliabilityDict(dict):
     """{ens_mse, ens_var, ssr: (C, L_total) fp32; rank_hist: (C, L_total, M + 1) int32; rank_hist_weighted: the same in fp32;
     n_invalid: (C, L_total) int32} over the four device buffers `ldc_rollout_reliability` fills"""
 
+    _spec = (_Buf(lambda Lt, M, C: (len(RELIABILITY_NAMES), C, Lt), torch.float32, float("nan"), 2), _Buf(lambda Lt, M, C: (C, Lt, M + 1), torch.int32, 0, 1),
+             _Buf(lambda Lt, M, C: (C, Lt, M + 1), torch.float32, 0, 1), _Buf(lambda Lt, M, C: (C, Lt), torch.int32, 0, 1))
+
     def __init__(self, buf, hist, hist_w, n_invalid):
         super().__init__({k: buf[i] for i, k in enumerate(RELIABILITY_NAMES)})
         self.update(rank_hist=hist, rank_hist_weighted=hist_w, n_invalid=n_invalid)
@@ -267,11 +325,7 @@ class ReliabilityDict(dict):
 
 def empty_reliability(M: int, C: int, L_total: int, device) -> ReliabilityDict:
     """the result of `rollout_reliability` before any column is written: scores NaN, histograms and `n_invalid` zero"""
-    n = len(RELIABILITY_NAMES)
-    return ReliabilityDict(torch.full((n, C, L_total), float("nan"), device=device, dtype=torch.float32),
-                           torch.zeros(C, L_total, M + 1, device=device, dtype=torch.int32),
-                           torch.zeros(C, L_total, M + 1, device=device, dtype=torch.float32),
-                           torch.zeros(C, L_total, device=device, dtype=torch.int32))
+    return ReliabilityDict(*_empty(ReliabilityDict._spec, L_total, device, M=M, C=C))
 
 
 @torch.no_grad()
@@ -289,30 +343,14 @@ def rollout_reliability(forecast: torch.Tensor, truth: torch.Tensor, lat_weight:
     forecast, `lead_dim`, `mean` / `std` / `target_std`: as `rollout_scores`.  truth: (C, L, H, W), or with `truth_slot` (one host int
     per lead time) an (N, C, H, W) table.  Returns a dict of device tensors with L_total = l_off + L columns (unwritten columns: NaN, empty
     histograms), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call returned."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    if not 1 <= M <= MAX_RELIABILITY_MEMBERS:
-        raise ValueError(f"{M} members: ldc_rollout_reliability serves 1 .. {MAX_RELIABILITY_MEMBERS}")
-    dev = f.device
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    w = _row_weight(lat_weight, H, dev, "lat_weight")
-    mn, sd = _channel_affine(mean, std, C, dev)
-    n = len(RELIABILITY_NAMES)
-    bufs = None
-    if out is not None:
-        bufs = getattr(out, "_buffers", None)
-        ok = bufs is not None and bufs[0].dim() == 3 and bufs[0].shape[:2] == (n, C) and all(b.is_contiguous() and b.device == dev for b in bufs)
-        if ok:
-            Lt = bufs[0].shape[2]
-            ok = bufs[1].shape == (C, Lt, M + 1) and bufs[2].shape == (C, Lt, M + 1) and bufs[3].shape == (C, Lt)
-        if not ok:
-            raise ValueError("out must be the dict an earlier rollout_reliability call returned for the same ensemble size and channels")
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slot), weight=(lat_weight, "lat_weight"),
+                  members=("ldc_rollout_reliability", MAX_RELIABILITY_MEMBERS))
+    bufs = _out_buffers(ReliabilityDict._spec, out, r, l_off, M=r.M, C=r.C, msg=(
+        "out must be the dict an earlier rollout_reliability call returned for the same ensemble size and channels"))
     hip._dev(forecast, truth, lat_weight, mean, std)
-    if bufs is None:
-        bufs = empty_reliability(M, C, l_off + L, dev)._buffers
-    slots = _upload_slots(t_slots, dev)
-    hip.rollout_reliability(f, t, slots, w, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
-                            channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mn, std=sd,
-                            target_std=target_std, nan_channel=sst_channel, L_total=bufs[0].shape[2], l_off=l_off)
+    bufs = bufs or _empty(ReliabilityDict._spec, l_off + r.L, r.f.device, M=r.M, C=r.C)
+    args, kw = _launch_args(r, bufs[0].shape[2], l_off)
+    hip.rollout_reliability(*args, *bufs, nan_channel=sst_channel, **kw)
     return ReliabilityDict(*bufs)
 
 
@@ -325,6 +363,8 @@ class SpectrumDict(dict):
     """{spec_members, spec_mean, spec_truth: (C, L_total, W / 2 + 1) fp32; n_invalid: (C, L_total) int32} over the two device buffers
     `ldc_rollout_spectrum` fills"""
 
+    _spec = (_Buf(lambda Lt, C, W: (len(SPECTRUM_NAMES), C, Lt, W // 2 + 1), torch.float32, float("nan"), 2), _Buf(lambda Lt, C, W: (C, Lt), torch.int32, 0, 1))
+
     def __init__(self, buf, n_invalid):
         super().__init__({k: buf[i] for i, k in enumerate(SPECTRUM_NAMES)})
         self.update(n_invalid=n_invalid)
@@ -333,8 +373,7 @@ class SpectrumDict(dict):
 
 def empty_spectrum(C: int, L_total: int, W: int, device) -> SpectrumDict:
     """the result of `rollout_spectrum` before any column is written: spectra NaN, `n_invalid` zero"""
-    return SpectrumDict(torch.full((len(SPECTRUM_NAMES), C, L_total, W // 2 + 1), float("nan"), device=device, dtype=torch.float32),
-                        torch.zeros(C, L_total, device=device, dtype=torch.int32))
+    return SpectrumDict(*_empty(SpectrumDict._spec, L_total, device, C=C, W=W))
 
 
 @torch.no_grad()
@@ -354,32 +393,18 @@ def rollout_spectrum(forecast: torch.Tensor, truth: torch.Tensor, row_weight: to
     caller's responsibility: the kernel treats a weight that is not > 0 as 0.  forecast, `lead_dim`, `mean` / `std` / `target_std`, truth /
     `truth_slot`, `out` / `l_off`: as `rollout_reliability`.  Returns a dict of device tensors with L_total = l_off + L columns (unwritten
     columns: NaN, `n_invalid` 0), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_spectrum`) returned."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    if W % 2 or not MIN_SPECTRUM_W <= W <= MAX_SPECTRUM_W:
-        raise ValueError(f"{W} points per row: ldc_rollout_spectrum serves even W in {MIN_SPECTRUM_W} .. {MAX_SPECTRUM_W}")
-    if not 1 <= M <= MAX_SPECTRUM_MEMBERS:
-        raise ValueError(f"{M} members: ldc_rollout_spectrum serves 1 .. {MAX_SPECTRUM_MEMBERS}")
-    dev = f.device
-    w = _row_weight(row_weight, H, dev, "row_weight")
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slot), weight=(row_weight, "row_weight"),
+                  members=("ldc_rollout_spectrum", MAX_SPECTRUM_MEMBERS))
+    if r.W % 2 or not MIN_SPECTRUM_W <= r.W <= MAX_SPECTRUM_W:
+        raise ValueError(f"{r.W} points per row: ldc_rollout_spectrum serves even W in {MIN_SPECTRUM_W} .. {MAX_SPECTRUM_W}")
     if not row_weight.is_cuda and not bool((row_weight >= 0).all()):  # NaN fails the comparison too
         raise ValueError("row_weight must be non-negative (0 leaves a row out) and not NaN")
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    mn, sd = _channel_affine(mean, std, C, dev)
-    n, K = len(SPECTRUM_NAMES), W // 2 + 1
-    bufs = None
-    if out is not None:
-        bufs = getattr(out, "_buffers", None)
-        ok = bufs is not None and len(bufs) == 2 and bufs[0].dim() == 4 and bufs[0].shape[:2] == (n, C) and bufs[0].shape[3] == K \
-            and bufs[0].dtype == torch.float32 and bufs[1].dtype == torch.int32 and all(b.is_contiguous() and b.device == dev for b in bufs)
-        if not (ok and bufs[1].shape == (C, bufs[0].shape[2])):
-            raise ValueError("out must be the dict an earlier rollout_spectrum call (or empty_spectrum) returned for the same channels and W")
+    bufs = _out_buffers(SpectrumDict._spec, out, r, l_off, C=r.C, W=r.W, msg=(
+        "out must be the dict an earlier rollout_spectrum call (or empty_spectrum) returned for the same channels and W"))
     hip._dev(forecast, truth, mean, std)
-    if bufs is None:
-        bufs = empty_spectrum(C, l_off + L, W, dev)._buffers
-    slots = _upload_slots(t_slots, dev)
-    hip.rollout_spectrum(f, t, slots, w, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2),
-                         channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs, mean=mn, std=sd,
-                         target_std=target_std, L_total=bufs[0].shape[2], l_off=l_off)
+    bufs = bufs or _empty(SpectrumDict._spec, l_off + r.L, r.f.device, C=r.C, W=r.W)
+    args, kw = _launch_args(r, bufs[0].shape[2], l_off)
+    hip.rollout_spectrum(*args, *bufs, **kw)
     return SpectrumDict(*bufs)
 
 
@@ -391,6 +416,8 @@ MAX_PRODUCT_MEMBERS, MAX_PRODUCT_SORT_MEMBERS = hip.PRODUCTS_MAX_MEMBERS, hip.PR
 class ProductsDict(dict):
     """{mean, std, min, max: (Cs, L_total, H, W); quantiles: (Q, Cs, L_total, H, W); exceed: (P, Cs, L_total, H, W)}, fp32 views over the
     three device buffers `ldc_rollout_products` fills; a buffer that is None (output not asked for) leaves its keys out"""
+
+    _spec = tuple(_Buf(lambda Lt, Cs, H, W, n, k=k: (n[k], Cs, Lt, H, W) if n[k] else None, torch.float32, float("nan"), 2, "kept") for k in range(3))  # n: planes of each
 
     def __init__(self, stats, quant, exceed):
         super().__init__()
@@ -405,9 +432,7 @@ class ProductsDict(dict):
 
 def empty_products(Cs: int, L_total: int, H: int, W: int, device, *, n_quantiles: int = 0, n_thresholds: int = 0, stats: bool = True) -> ProductsDict:
     """the result of `rollout_products` before any column is written: NaN everywhere"""
-    new = lambda n: torch.full((n, Cs, L_total, H, W), float("nan"), device=device, dtype=torch.float32)  # noqa: E731
-    return ProductsDict(new(len(PRODUCT_STAT_NAMES)) if stats else None, new(n_quantiles) if n_quantiles else None,
-                        new(n_thresholds) if n_thresholds else None)
+    return ProductsDict(*_empty(ProductsDict._spec, L_total, device, Cs=Cs, H=H, W=W, n=(len(PRODUCT_STAT_NAMES) if stats else 0, n_quantiles, n_thresholds)))
 
 
 @torch.no_grad()
@@ -426,10 +451,9 @@ def rollout_products(forecast: torch.Tensor, *, quantiles=(), thresholds=None, t
     indexed by the original channel.  `stats=False` leaves mean / std / min / max out.  forecast, `lead_dim`, `mean` / `std` /
     `target_std`: as `rollout_scores`.  Returns a `ProductsDict` of device views with L_total = l_off + L columns (unwritten columns NaN),
     or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_products`) returned."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
+    r = _prologue(forecast, lead_dim, mean, std, target_std, members=("ldc_rollout_products", MAX_PRODUCT_MEMBERS))
+    M, C, H, W, dev = r.M, r.C, r.H, r.W, r.f.device
     qs = [float(q) for q in (quantiles.tolist() if isinstance(quantiles, torch.Tensor) else quantiles)]
-    if not 1 <= M <= MAX_PRODUCT_MEMBERS:
-        raise ValueError(f"{M} members: ldc_rollout_products serves 1 .. {MAX_PRODUCT_MEMBERS}")
     if qs and M > MAX_PRODUCT_SORT_MEMBERS:
         raise ValueError(f"{M} members: quantiles need the members sorted in registers, at most {MAX_PRODUCT_SORT_MEMBERS}")
     if channels is None:
@@ -455,33 +479,18 @@ def rollout_products(forecast: torch.Tensor, *, quantiles=(), thresholds=None, t
         raise ValueError("nothing to compute: no stats, no quantiles, no thresholds")
     if l_off < 0:
         raise ValueError("l_off must not be negative")
-    dev = f.device
-    mn, sd = _channel_affine(mean, std, C, dev)
-    bufs = None
-    if out is not None:
-        bufs = getattr(out, "_buffers", None)
-        ok = bufs is not None and len(bufs) == 3
-        if ok:
-            want = (len(PRODUCT_STAT_NAMES) if stats else 0, Q, P)
-            Lt = next((b.shape[2] for b in bufs if b is not None and b.dim() == 5), None)
-            ok = Lt is not None and l_off + L <= Lt
-            for b, n in zip(bufs, want):
-                if n == 0:
-                    continue  # not asked for in this call: left alone
-                ok = ok and b is not None and tuple(b.shape) == (n, Cs, Lt, H, W) and b.dtype == torch.float32 and b.is_contiguous() and b.device == dev
-        if not ok:
-            raise ValueError("out must be the dict an earlier rollout_products call (or empty_products) returned for the same channels, "
-                             "quantiles, thresholds and grid, with room for columns l_off .. l_off + L - 1")
+    bufs = _out_buffers(ProductsDict._spec, out, r, l_off, Cs=Cs, H=H, W=W,
+                                                 n=(len(PRODUCT_STAT_NAMES) if stats else 0, Q, P), msg=(
+        "out must be the dict an earlier rollout_products call (or empty_products) returned for the same channels, "
+        "quantiles, thresholds and grid, with room for columns l_off .. l_off + L - 1"))
     hip._dev(forecast)
-    if bufs is None:
-        bufs = empty_products(Cs, l_off + L, H, W, dev, n_quantiles=Q, n_thresholds=P, stats=stats)._buffers
-    st, qu, ex = (b if n else None for b, n in zip(bufs, (stats, Q, P)))
+    bufs = bufs or empty_products(Cs, l_off + r.L, H, W, dev, n_quantiles=Q, n_thresholds=P, stats=stats)._buffers
+    st, qu, ex = (b if n else None for b, n in zip(bufs, (stats, Q, P)))  # a buffer not asked for in this call is left alone
     L_total = next(b.shape[2] for b in (st, qu, ex) if b is not None)
     chan_d = None if chan is None else _upload_slots(chan, dev)
     thr_d = None if P == 0 else (thresholds if thresholds.is_cuda else hip.upload_nonblocking(thresholds.contiguous(), dev)).contiguous()
-    hip.rollout_products(f, desc, M=M, C=C, Cs=Cs, L=L, H=H, W=W, member_stride=f.stride(0), lead_stride=f.stride(2), channel_stride=f.stride(1),
-                         channels=chan_d, thr=thr_d, stats=st, quant=qu, exceed=ex, mean=mn, std=sd, target_std=target_std, L_total=L_total,
-                         l_off=l_off)
+    args, kw = _launch_args(r, L_total, l_off)
+    hip.rollout_products(*args, desc, Cs=Cs, channels=chan_d, thr=thr_d, stats=st, quant=qu, exceed=ex, **kw)
     return ProductsDict(*bufs)
 
 
@@ -503,6 +512,9 @@ class EventsDict(dict):
     three device buffers `ldc_rollout_events` fills: entry [e, l, n, o] holds the points at which n members show event e and the truth
     does (o = 1) or does not (o = 0)"""
 
+    _spec = (_Buf(lambda Lt, M, E: (E, Lt, M + 1, 2), torch.int32, 0, 1), _Buf(lambda Lt, M, E: (E, Lt, M + 1, 2), torch.float32, 0, 1),
+             _Buf(lambda Lt, M, E: (E, Lt), torch.int32, 0, 1))
+
     def __init__(self, hist, hist_w, n_invalid):
         super().__init__(event_hist=hist, event_hist_weighted=hist_w, event_n_invalid=n_invalid)
         self._buffers = (hist, hist_w, n_invalid)
@@ -510,9 +522,7 @@ class EventsDict(dict):
 
 def empty_events(M: int, E: int, L_total: int, device) -> EventsDict:
     """the result of `rollout_events` before any column is written: empty histograms, `event_n_invalid` zero"""
-    return EventsDict(torch.zeros(E, L_total, M + 1, 2, device=device, dtype=torch.int32),
-                      torch.zeros(E, L_total, M + 1, 2, device=device, dtype=torch.float32),
-                      torch.zeros(E, L_total, device=device, dtype=torch.int32))
+    return EventsDict(*_empty(EventsDict._spec, L_total, device, M=M, E=E))
 
 
 def _event_list(events, C: int, has_clim: bool):
@@ -554,37 +564,19 @@ def rollout_events(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torc
     `clim_slots`: as `rollout_scores`; needed by anomaly events only.  Returns an `EventsDict` of device tensors with L_total = l_off + L
     columns (unwritten columns: empty histograms), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or
     `empty_events`) returned for the same ensemble size and number of events."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    if not 1 <= M <= MAX_EVENT_MEMBERS:
-        raise ValueError(f"{M} members: ldc_rollout_events serves 1 .. {MAX_EVENT_MEMBERS}")
-    dev = f.device
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
-    w = _row_weight(lat_weight, H, dev, "lat_weight")
-    mn, sd = _channel_affine(mean, std, C, dev)
-    desc = hip.events_desc(_event_list(events, C, clim is not None))
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slot), clim=(clim, clim_slots), weight=(lat_weight, "lat_weight"),
+                  members=("ldc_rollout_events", MAX_EVENT_MEMBERS))
+    desc = hip.events_desc(_event_list(events, r.C, clim is not None))
     E = desc.n_events
     if l_off < 0:
         raise ValueError("l_off must not be negative")
-    bufs = None
-    if out is not None:
-        bufs = getattr(out, "_buffers", None)
-        ok = bufs is not None and len(bufs) == 3 and bufs[0].dim() == 4 and all(b.is_contiguous() and b.device == dev for b in bufs)
-        if ok:
-            Lt = bufs[0].shape[1]
-            ok = l_off + L <= Lt and tuple(bufs[0].shape) == (E, Lt, M + 1, 2) and bufs[1].shape == bufs[0].shape and tuple(bufs[2].shape) == (E, Lt) \
-                and bufs[0].dtype == torch.int32 and bufs[1].dtype == torch.float32 and bufs[2].dtype == torch.int32
-        if not ok:
-            raise ValueError("out must be the dict an earlier rollout_events call (or empty_events) returned for the same ensemble size and "
-                             "number of events, with room for columns l_off .. l_off + L - 1")
+    bufs = _out_buffers(EventsDict._spec, out, r, l_off, M=r.M, E=E, msg=(
+        "out must be the dict an earlier rollout_events call (or empty_events) returned for the same ensemble size and "
+        "number of events, with room for columns l_off .. l_off + L - 1"))
     hip._dev(forecast, truth, clim, lat_weight, mean, std)
-    if bufs is None:
-        bufs = empty_events(M, E, l_off + L, dev)._buffers
-    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], dev)
-    hip.rollout_events(f, t, slots[0], c, None if c is None else slots[1], w, desc, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0),
-                       lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs,
-                       clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mn, std=sd, target_std=target_std, L_total=bufs[0].shape[1],
-                       l_off=l_off)
+    bufs = bufs or _empty(EventsDict._spec, l_off + r.L, r.f.device, M=r.M, E=E)
+    args, kw = _launch_args(r, bufs[0].shape[1], l_off)
+    hip.rollout_events(*args, desc, *bufs, **kw)
     return EventsDict(*bufs)
 
 
@@ -650,6 +642,8 @@ class FssDict(dict):
     """{event_fss_sums: (E, S, L_total, 6) float64; event_fss_n_invalid: (E, L_total) int32} over the two device buffers `ldc_rollout_fss`
     fills: entry [e, s, l] holds the sums of `FSS_SUM_NAMES` over the contributing centres of event e at radius s"""
 
+    _spec = (_Buf(lambda Lt, E, S: (E, S, Lt, len(FSS_SUM_NAMES)), torch.float64, 0, 2), _Buf(lambda Lt, E, S: (E, Lt), torch.int32, 0, 1))
+
     def __init__(self, sums, n_invalid):
         super().__init__(event_fss_sums=sums, event_fss_n_invalid=n_invalid)
         self._buffers = (sums, n_invalid)
@@ -657,8 +651,7 @@ class FssDict(dict):
 
 def empty_fss(E: int, S: int, L_total: int, device) -> FssDict:
     """the result of `rollout_fss` before any column is written: zeros"""
-    return FssDict(torch.zeros(E, S, L_total, len(FSS_SUM_NAMES), device=device, dtype=torch.float64),
-                   torch.zeros(E, L_total, device=device, dtype=torch.int32))
+    return FssDict(*_empty(FssDict._spec, L_total, device, E=E, S=S))
 
 
 def _radius_list(radii, W: int):
@@ -696,38 +689,20 @@ def rollout_fss(forecast: torch.Tensor, truth: torch.Tensor, lat_weight: torch.T
     Every other argument, `out` / `l_off` included, as `rollout_events`.  Returns an `FssDict` of device tensors with L_total = l_off + L
     columns (unwritten columns: zeros), or fills columns l_off .. l_off + L - 1 of `out`, the dict an earlier call (or `empty_fss`)
     returned for the same number of events and radii."""
-    f, M, C, L, H, W = _forecast_view(forecast, lead_dim)
-    if not 1 <= M <= MAX_EVENT_MEMBERS:
-        raise ValueError(f"{M} members: ldc_rollout_fss serves 1 .. {MAX_EVENT_MEMBERS}")
-    dev = f.device
-    t, t_ss, t_cs, t_slots = _plane_table(truth, truth_slot, C, L, H, W, "truth")
-    c, c_ss, c_cs, c_slots = (None, 0, 0, None) if clim is None else _plane_table(clim, clim_slots, C, L, H, W, "clim")
-    w = _row_weight(lat_weight, H, dev, "lat_weight")
-    mn, sd = _channel_affine(mean, std, C, dev)
-    desc = hip.events_desc(_event_list(events, C, clim is not None))
-    rs = _radius_list(radii, W)
+    r = _prologue(forecast, lead_dim, mean, std, target_std, truth=(truth, truth_slot), clim=(clim, clim_slots), weight=(lat_weight, "lat_weight"),
+                  members=("ldc_rollout_fss", MAX_EVENT_MEMBERS))
+    desc = hip.events_desc(_event_list(events, r.C, clim is not None))
+    rs = _radius_list(radii, r.W)
     E, S = desc.n_events, len(rs)
     if l_off < 0:
         raise ValueError("l_off must not be negative")
-    bufs = None
-    if out is not None:
-        bufs = getattr(out, "_buffers", None)
-        ok = bufs is not None and len(bufs) == 2 and bufs[0].dim() == 4 and all(b.is_contiguous() and b.device == dev for b in bufs)
-        if ok:
-            Lt = bufs[0].shape[2]
-            ok = l_off + L <= Lt and tuple(bufs[0].shape) == (E, S, Lt, len(FSS_SUM_NAMES)) and tuple(bufs[1].shape) == (E, Lt) \
-                and bufs[0].dtype == torch.float64 and bufs[1].dtype == torch.int32
-        if not ok:
-            raise ValueError("out must be the dict an earlier rollout_fss call (or empty_fss) returned for the same number of events and "
-                             "radii, with room for columns l_off .. l_off + L - 1")
+    bufs = _out_buffers(FssDict._spec, out, r, l_off, E=E, S=S, msg=(
+        "out must be the dict an earlier rollout_fss call (or empty_fss) returned for the same number of events and "
+        "radii, with room for columns l_off .. l_off + L - 1"))
     hip._dev(forecast, truth, clim, lat_weight, mean, std)
-    if bufs is None:
-        bufs = empty_fss(E, S, l_off + L, dev)._buffers
-    slots = _upload_slots([t_slots, c_slots if c_slots is not None else t_slots], dev)
-    hip.rollout_fss(f, t, slots[0], c, None if c is None else slots[1], w, desc, rs, *bufs, M=M, C=C, L=L, H=H, W=W, member_stride=f.stride(0),
-                    lead_stride=f.stride(2), channel_stride=f.stride(1), truth_slot_stride=t_ss, truth_channel_stride=t_cs,
-                    clim_slot_stride=c_ss, clim_channel_stride=c_cs, mean=mn, std=sd, target_std=target_std, L_total=bufs[0].shape[2],
-                    l_off=l_off)
+    bufs = bufs or _empty(FssDict._spec, l_off + r.L, r.f.device, E=E, S=S)
+    args, kw = _launch_args(r, bufs[0].shape[2], l_off)
+    hip.rollout_fss(*args, desc, rs, *bufs, **kw)
     return FssDict(*bufs)
 
 

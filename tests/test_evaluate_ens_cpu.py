@@ -129,9 +129,11 @@ def test_lat_weights():
     assert w48.shape == (48,) and np.allclose(w48.numpy(), np.cos(np.deg2rad(lat48)) / np.cos(np.deg2rad(lat48)).mean(), rtol=1e-6, atol=1e-7)
 
 
-# ---- the forecast view the five rollout wrappers share: one exception per mistake, before the device is asked for -----------------------------
+# ---- the prologue the nine rollout wrappers share: one exception per mistake, before the device is asked for -----------------------------
 _M, _C, _L, _H, _W = 2, 1, 1, 3, 8
-_WRAPPERS = ("rollout_scores", "validation_scores", "rollout_reliability", "rollout_spectrum", "rollout_products")
+_WRAPPERS = ("rollout_scores", "validation_scores", "rollout_reliability", "rollout_spectrum", "rollout_products", "rollout_events", "rollout_fss",
+             "rollout_regional", "rollout_energy")
+_CHECK_L_OFF = _WRAPPERS[4:]  # these refuse a negative l_off on the host; the four older ones pass it to the library
 
 
 def _wrapper_call(name, *, forecast=None, weight=None, **kw):
@@ -148,6 +150,12 @@ def _wrapper_call(name, *, forecast=None, weight=None, **kw):
         return E.rollout_reliability(x, t, w, -1, **kw)
     if name == "rollout_products":
         return E.rollout_products(x, **kw)
+    if name == "rollout_events":
+        return E.rollout_events(x, t, w, [E.Event(0, "gt", 0.5)], **kw)
+    if name == "rollout_fss":
+        return E.rollout_fss(x, t, w, [E.Event(0, "gt", 0.5)], [0, 1], **kw)
+    if name == "rollout_regional":
+        return E.rollout_regional(x, t, w, np.ones((_H, _W), dtype=np.uint32), 1, **kw)
     return getattr(E, name)(x, t, w, **kw)
 
 
@@ -165,6 +173,8 @@ def test_rollout_wrappers_share_their_argument_errors(name):
     if name != "rollout_products":  # no weight there
         what = "row_weight" if name == "rollout_spectrum" else "lat_weight"
         cases.append((dict(weight=torch.ones(_H + 1)), ValueError, f"{what} must have one value per latitude row"))
+    if name in _CHECK_L_OFF:
+        cases.append((dict(l_off=-1), ValueError, "l_off must not be negative"))
     for kw, exc, match in cases:
         with pytest.raises(exc, match=match):
             _wrapper_call(name, **kw)

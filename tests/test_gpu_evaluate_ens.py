@@ -177,3 +177,42 @@ def test_cli_round_trip(setup, tmp_path, in_memory):
         assert _same_bits(torch.from_numpy(np.load(out_dir / f"{ts}_{k}.npy")), want[k]), k
         assert _same_bits(torch.from_numpy(res[k][0]), want[k]) and np.array_equal(np.load(out_dir / f"{k}.npy"), res[k], equal_nan=True)
         assert np.isfinite(res[k]).all()
+
+
+@pytest.mark.parametrize("dbf", [3, 6])
+def test_every_metric_at_once_is_each_metric_alone(setup, dbf):
+    """every optional metric switched on in one call: each returned tensor is the bits (NaN pattern included) of the call with only
+    that metric on, the five base scores are the bits of a call with none, and the key set is exactly the union; total_num_steps = 4
+    leaves one column unwritten"""
+    from ladcast_amd.evaluate import evaluate_ens_gpu as EG
+    from ladcast_amd.evaluate.energy import EnergyGroup
+    from ladcast_amd.evaluate.regional import Region
+    from ladcast_amd.evaluate.utils import Event
+
+    s = setup
+    args = (s["latents"], s["g"], s["mean"], s["std"], s["truth"].cuda(), TRUTH_SLOTS, s["clim"].cuda(), s["clim_slots"], s["lat_w"])
+    kw = dict(sst_channel=SST, crop_init=True, decode_batch_frames=dbf, total_num_steps=T + 1)
+    events = [Event(0, "gt", float(s["mean"][0])), Event(SST, "lt", 0.0, True)]  # the second: an anomaly event on the SST channel
+    regions = [Region("box", -20.0, 20.0, 30.0, 120.0), Region("across", 10.0, 60.0, 340.0, 20.0)]  # the second crosses 0 degrees east
+    alone = dict(reliability=(dict(reliability=True), EG.RELIABILITY_KEYS),
+                 spectrum=(dict(spectrum=True), EG.SPECTRUM_KEYS),
+                 events=(dict(events=events), EG.EVENTS_KEYS),
+                 fss=(dict(events=events, fss_radii=(0, 2)), EG.EVENTS_KEYS + EG.FSS_KEYS),
+                 regional=(dict(regions=regions), EG.REGIONAL_KEYS),
+                 energy=(dict(energy=True, energy_groups=[EnergyGroup("pair", (0, 1))]), EG.ENERGY_KEYS + EG.ENERGY_GROUP_NAMES))
+    every = {}
+    for opts, _ in alone.values():
+        every.update(opts)
+    got = EG.score_latent_rollout(*args, **every, **kw)
+    plain = EG.score_latent_rollout(*args, **kw)
+    assert set(plain) == set(KEYS)
+    assert set(got) == set(KEYS).union(*(keys for _, keys in alone.values()))
+    assert all(v.device.type == "cpu" for v in got.values())
+    for k in KEYS:
+        assert got[k].shape == (C, T + 1) and _same_bits(got[k], plain[k]), k
+        assert bool(torch.isnan(got[k][:, T]).all()) and bool(torch.isfinite(got[k][:, :T]).all()), k
+    for name, (opts, keys) in alone.items():
+        one = EG.score_latent_rollout(*args, **opts, **kw)
+        assert set(one) == set(KEYS) | set(keys), name
+        for k in KEYS + tuple(keys):
+            assert got[k].dtype == one[k].dtype and _same_bits(got[k], one[k]), (name, k)
