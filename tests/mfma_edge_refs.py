@@ -42,6 +42,11 @@ Attention  O = softmax(q k^T + bias) v, per (batch, head), scores in log2 units 
 
 Convs: the GEMM bound with K = ks * ks * cin_padded on the float64 sphere conv of oracle/sphere_conv.py (the zero taps of a padded cin
 add no error but are counted: the bound only grows).
+
+The tile-per-workgroup kernel of gemm_f32.hip (ldc_gemm_bias_act, ldc_sphere_conv_nhwc) sums a tile in one piece, K products in k order:
+the same n = K + 10 holds it (the 9 pieces are counted though it has none).  Its conv at H = 2, where oracle/sphere_conv.py and the
+reference raise, is DEFINED by the float64 gather-GEMM over sphere_gather (conv_ref(via_gather=True)), which equals the oracle conv
+wherever that exists.
 """
 from __future__ import annotations
 
@@ -103,11 +108,12 @@ def gemm_ref(A, W, bias=None, gate=None, R=None, act=0, mode="f32"):
 
 
 def gemm_f32(A, W, bias=None, gate=None, R=None, act=0, mode="f32", cuts=(), drop_kstep=None, drop_lohi_panel=None, last_row_from_prev=False,
-             piece_twice=False):
+             piece_twice=False, stale_stage=False):
     """The kernels' arithmetic in fp32 torch: per 128 x 128 tile an fp32 accumulator that takes one k-step (32, or 64 single-term, values of
     every term) at a time; `cuts` (k-step indices) end a piece, the pieces are summed in order.  Planted defects:
       drop_kstep = (bm, bn, kt): that k-step of that tile is skipped;  drop_lohi_panel = bn: the al.wh term is missing in column panel bn;
-      last_row_from_prev: row M - 1 is computed from row M - 2 of A;  piece_twice: the first piece of tile (0, 0) is added twice."""
+      last_row_from_prev: row M - 1 is computed from row M - 2 of A;  piece_twice: the first piece of tile (0, 0) is added twice;
+      stale_stage: k-step kt >= 2 multiplies the operands of k-step kt - 2 (a double-buffered LDS stage read before it was refilled)."""
     B, M, K = A.shape
     N = W.shape[0]
     ks = KSTEP[mode]
@@ -124,7 +130,8 @@ def gemm_f32(A, W, bias=None, gate=None, R=None, act=0, mode="f32", cuts=(), dro
                     acc = torch.zeros_like(acc)
                 if drop_kstep == (bm // 128, bn // 128, kt):
                     continue
-                k0, k1 = kt * ks, min(K, kt * ks + ks)
+                src = kt - 2 if stale_stage and kt >= 2 else kt
+                k0, k1 = src * ks, min(K, src * ks + ks)
                 for ti, (a, w) in enumerate(terms):
                     if ti == 2 and drop_lohi_panel == bn // 128:
                         continue
@@ -191,6 +198,24 @@ def gemm_shapes(mode, regstage=False):
             for N in GEMM_N + (GEMM_N_SCALAR,):
                 i += 1
                 yield M, N, K, (1, 3)[i % 2], i % len(EPILOGUES)
+
+
+# the tile-per-workgroup kernel of gemm_f32.hip (ldc_gemm_bias_act): 4 = one float4 in one ragged k-tile; 36 = one whole tile and a ragged one of
+# a single float4; 64 = two tiles, both LDS stages; 84 = the embedders' depth; 96 = three tiles, stage 0 reused
+TILE_GEMM_K = (4, 36, 64, 84, 96)
+TILE_GEMM_N = (5,) + GEMM_N + (GEMM_N_SCALAR,)
+
+
+def tile_gemm_shapes(K=None):
+    """(M, N, K, batch, epilogue variant) of every case of the tile-per-workgroup GEMM (mode "f32"), batch and epilogue taking turns as in
+    gemm_shapes; K: only the cases of that depth (the turns are those of the whole table)"""
+    i = 0
+    for k in TILE_GEMM_K:
+        for M in GEMM_M:
+            for N in TILE_GEMM_N:
+                i += 1
+                if K is None or k == K:
+                    yield M, N, k, (1, 3)[i % 2], i % len(EPILOGUES)
 
 
 def sweep_K(mode, k32):
@@ -389,9 +414,19 @@ def _oracle_conv(x_nchw, w, bias, ks):
         return m(x_nchw)
 
 
-def conv_ref(x, w, bias, ks, mode, act=0, R=None):
+def _gather_conv(x_nchw, w, ks):
+    """float64 sphere conv as the gather-GEMM: sum over taps and channels of sphere_gather(x) . w, defined index by index at any H >= 2"""
+    cout, cin = w.shape[:2]
+    g = sphere_gather(x_nchw.permute(0, 2, 3, 1), ks)  # [B][H][W][ks * ks][cin]
+    return torch.einsum("bhwtc,otc->bohw", g, w.permute(0, 2, 3, 1).reshape(cout, ks * ks, cin))
+
+
+def conv_ref(x, w, bias, ks, mode, act=0, R=None, via_gather=False):
     """x [B][H][W][cin] NHWC fp32, w [cout][cin][ks][ks], bias [cout] | None, R [B][H][W][cout] | None -> float64 (y, bound) NHWC: the float64
-    sphere conv of every term of `mode`, the GEMM bound with K = ks * ks * padded cin"""
+    sphere conv of every term of `mode`, the GEMM bound with K = ks * ks * padded cin.  via_gather: the float64 gather-GEMM over
+    sphere_gather instead of oracle/sphere_conv.py - the two agree at every H >= 3 (judged on the CPU); at H = 2, where the oracle and the
+    reference both raise (their middle slice has fewer than ks rows), the gather IS the definition"""
+    conv = (lambda a, ww, b, k: _gather_conv(a, ww, k)) if via_gather else _oracle_conv
     xn = x.permute(0, 3, 1, 2)
     if mode == "f32":
         terms = [(xn.float(), w.float())]
@@ -401,8 +436,8 @@ def conv_ref(x, w, bias, ks, mode, act=0, R=None):
         terms = [(xh, wh), (xh, wl), (xl, wh)] if mode == "bf16x3" else [(xh, wh)]
     y = s = 0
     for a, ww in terms:
-        y = y + _oracle_conv(a.double(), ww.double(), None, ks)
-        s = s + _oracle_conv(a.double().abs(), ww.double().abs(), None, ks)
+        y = y + conv(a.double(), ww.double(), None, ks)
+        s = s + conv(a.double().abs(), ww.double().abs(), None, ks)
     cout, cin = w.shape[:2]
     b = torch.zeros(cout, dtype=torch.float64) if bias is None else bias.double()
     y, s = y.permute(0, 2, 3, 1) + b, s.permute(0, 2, 3, 1) + b.abs()
@@ -413,31 +448,38 @@ def conv_ref(x, w, bias, ks, mode, act=0, R=None):
     return v.reshape(B, H, W_, cout), bv.reshape(B, H, W_, cout)
 
 
-def sphere_gather(x, ks, wrap_wrong_side=False):
+def sphere_gather(x, ks, wrap_wrong_side=False, no_pole_roll=False, no_pole_flip=False, tile_first_image=False):
     """x [B][H][W][C] -> [B][H][W][ks * ks][C]: the source pixel of every tap under the sphere padding rule, written out index by index
     (rows past a pole: mirrored and rolled by W / 2; columns wrap; the oracle's flipped kernel rows at the poles are this gather).
-    wrap_wrong_side (planted defect): the column that wraps around is taken from the side it is on - clamped instead of wrapped."""
+    Planted defects:  wrap_wrong_side: the column that wraps around is taken from the side it is on - clamped instead of wrapped;
+      no_pole_roll: a row past a pole is mirrored but not shifted by W / 2;  no_pole_flip: the kx flip at rows 0 and H - 1 is missing;
+      tile_first_image: a pixel gathers from the image that holds the first pixel of its 128-row tile (one image base per tile)."""
     B, H, W_, C = x.shape
     p = ks // 2
     h, ky, kx = torch.arange(H)[:, None, None, None], torch.arange(ks)[None, None, :, None], torch.arange(ks)[None, None, None, :]
     flip = ((h == 0) & (ky < p)) | ((h == H - 1) & (ky >= ks - p))  # at the two pole rows the kernel rows over the pole are flipped left-right
-    kx = torch.where(flip, ks - 1 - kx, kx.expand(H, 1, ks, ks))
+    kx = kx.expand(H, 1, ks, ks) if no_pole_flip else torch.where(flip, ks - 1 - kx, kx.expand(H, 1, ks, ks))
     hh = (h + ky - p).expand(H, W_, ks, ks)
     ww = (torch.arange(W_)[None, :, None, None] + kx - p).expand(H, W_, ks, ks)
     over = (hh < 0) | (hh >= H)
     hs = torch.where(hh < 0, -1 - hh, torch.where(hh >= H, 2 * H - 1 - hh, hh))
-    ws = torch.where(over, ww + W_ // 2, ww)
+    ws = ww if no_pole_roll else torch.where(over, ww + W_ // 2, ww)
     ws = ws.clamp(0, W_ - 1) if wrap_wrong_side else ws % W_
+    if tile_first_image:
+        pix = torch.arange(B * H * W_).reshape(B, H, W_)
+        img = (pix // 128 * 128 // (H * W_))[..., None, None]
+        return x[img, hs, ws].reshape(B, H, W_, ks * ks, C)
     return x[:, hs, ws].reshape(B, H, W_, ks * ks, C)
 
 
-def conv_f32(x, w, bias, ks, mode, act=0, R=None, wrap_wrong_side=False):
-    """the implicit GEMM in fp32: gathered rows [pix][tap][cin] . W[cout][tap][cin], through gemm_f32's chunked accumulation"""
+def conv_f32(x, w, bias, ks, mode, act=0, R=None, **defects):
+    """the implicit GEMM in fp32: gathered rows [pix][tap][cin] . W[cout][tap][cin], through gemm_f32's chunked accumulation; defects: the
+    planted defects of sphere_gather"""
     B, H, W_, cin = x.shape
     cout = w.shape[0]
     cp = conv_cin_padded(cin, KSTEP[mode])
     a = torch.zeros(B, H, W_, ks * ks, cp)
-    a[..., :cin] = sphere_gather(x, ks, wrap_wrong_side)
+    a[..., :cin] = sphere_gather(x, ks, **defects)
     wt = torch.zeros(cout, ks * ks, cp)
     wt[..., :cin] = w.permute(0, 2, 3, 1).reshape(cout, ks * ks, cin)
     y = gemm_f32(a.reshape(1, B * H * W_, ks * ks * cp), wt.reshape(cout, ks * ks * cp), bias, None, None if R is None else R.reshape(1, B * H * W_, cout),
@@ -447,6 +489,18 @@ def conv_f32(x, w, bias, ks, mode, act=0, R=None, wrap_wrong_side=False):
 
 # (B, H, W, cin, cout, ks, residual): cin tails 40 / 28, ragged output panels 136 / 86, two frames
 CONV_CASES = [(2, 4, 8, 40, 136, 3, True), (2, 3, 6, 28, 86, 5, False), (2, 5, 4, 40, 86, 1, True), (2, 6, 12, 28, 136, 3, False)]
+# the tile-per-workgroup conv of gemm_f32.hip (ldc_sphere_conv_nhwc), each with act 0 and 1:
+TILE_CONV_CASES = [
+    (2, 4, 8, 40, 136, 3, True),  # 64 pixels: both images in one 128-row tile; cin 40 = two k-tiles per tap, the second ragged; ragged output panel
+    (3, 6, 12, 28, 136, 3, False),  # 216 pixels: two row tiles, the second ragged, image boundaries at 72 and 144 inside tiles; one ragged k-tile per tap
+    (2, 3, 8, 28, 86, 5, False),  # 5 x 5 at H = 3: every output row reaches over a pole, the middle one over both with unflipped kernel rows
+    (2, 5, 4, 40, 86, 5, True),  # 5 x 5 at W = 4: the roll by W / 2 and the wrap can apply to the same column
+    (2, 3, 2, 4, 5, 3, True),  # the narrowest width, the smallest cin and cout
+    (1, 3, 4, 68, 8, 5, True),  # three k-tiles per tap, the last one holding one float4
+]
+TILE_CONV_STRADDLING = TILE_CONV_CASES[:2]  # a 128-row tile holds pixels of more than one image, the first of them of image 0
+TILE_CONV_H2_CASE = (2, 2, 4, 8, 8, 3, False)  # H = 2: defined by sphere_gather (conv_ref(via_gather=True)), not by the oracle
+MODULE_CONV_CASE = (2, 4, 8, 6, 5, 3, False)  # ladcast_amd.models.SphereConv2d(6, 5, 3, 1, 1) on (2, 6, 4, 8): cin padded to 8 with zero weights
 # the smallest (frames, H, W) at cin 40, cout 136 that ldc_sphere_conv_plan hands to the halo-staged kernel (the GPU test searches and asserts it)
 HALO_CASE = (16, 18, 36, 40, 136, 3, True)
 

@@ -10,13 +10,19 @@ to the dispatcher's own choice, without an environment variable.  The attentions
 S / Sq / bias table and, at one 260-unit shape, the other schedules: the exact-fp32 kernel's 4-wave form and balanced cut, the split
 kernel's persistent form with its key-sliced tail and merge launch - each shown to have run by what it leaves in its workspace.
 
-Not covered here: the tile-per-workgroup conv `ldc_sphere_conv_nhwc` and the single-launch entry `ldc_gemm_bias_act`; three pieces of one
-tile in the single-term mode (K <= 768 gives it 12 k-steps, which no rule cuts: its pieces come from the sweeps of the other problem sets).
+The tile-per-workgroup kernel of gemm_f32.hip runs behind its own two entry points, `ldc_gemm_bias_act` (175 shapes over the ragged
+depths 4 / 36 / 84 and the LDS-stage depths 64 / 96, W strided too) and `ldc_sphere_conv_nhwc` (six cases at act 0 and 1: tiles that
+straddle images, ragged channel tiles, 5 x 5 kernels at H = 3 and W = 4, the narrowest width; H = 2 against the float64 gather-GEMM; one
+case through `ladcast_amd.models.SphereConv2d` with cin padded by zero weights), under the same method plus the same bits on a second
+launch; every argument the two entry points refuse is passed once, with the status asserted and the outputs still unwritten.
+
+Not covered here: the pixel-count refusal of `ldc_sphere_conv_nhwc` (see test_tile_conv_refusals); three pieces of one tile in the
+single-term mode (K <= 768 gives it 12 k-steps, which no rule cuts: its pieces come from the sweeps of the other problem sets).
 
 LDC_MFMA_EDGE_RATIOS=<file>: the worst err / bound ratio of every case is written there as JSON (profiles/mfma_edge_worst_ratios.json)."""
 import json
 import os
-from ctypes import c_void_p
+from ctypes import byref, c_void_p
 
 import pytest
 import torch
@@ -111,13 +117,15 @@ PATHS = {
     "bf16 single term": ("bf16", FMT_BF16, 1 | 4, True, True),
     "bf16 single term, bf16 C": ("bf16", FMT_BF16, 1 | 2 | 4, True, True),
 }
+TILE_PATH = "f32 tile-per-workgroup"  # ldc_gemm_bias_act: its own entry point, not a path of the grouped ones
+TILE_PATHS = {TILE_PATH: ("f32", FMT_F32, 0, False, True)}
 
 
 class Gemm:
     """the guarded operands of one GEMM problem on one path, and its launch struct"""
 
     def __init__(self, hip, path, M, N, K, batch, epi, c_fmt=None, rows_layout=False, inputs=R.gemm_inputs):
-        mode, a_fmt, flags, self.split_entry, strided_w = PATHS[path]
+        mode, a_fmt, flags, self.split_entry, strided_w = PATHS[path] if path in PATHS else TILE_PATHS[path]
         has_bias, has_gate, res, act, col0 = R.EPILOGUES[epi]
         kw = inputs(M, N, K, batch, epi, mode)
         self.c_fmt = c_fmt = (0 if not flags & 2 else FMT_SPLIT if mode == "bf16x3" else FMT_BF16) if c_fmt is None else c_fmt
@@ -410,3 +418,171 @@ def test_halo_conv_edges(hip, mode):
     # the plan assumes the full grouped-GEMM workspace (two workgroups per tile need 2 x 128 KiB per tile; with less the gathered kernel runs)
     assert COUNTER_BYTES + 2 * 512 * SLOT_BYTES == hip.lib.ldc_gemm_grouped_workspace_bytes()
     _run_conv(hip, mode, R.HALO_CASE, act=0, expect_halo=True, ws_ranges=512)
+
+
+# ---- the tile-per-workgroup kernel of gemm_f32.hip: ldc_gemm_bias_act -----------------------------------------------------------------
+ERR_ALIGN, ERR_UNSUPPORTED = -2, -3
+VP = lambda g: None if g is None else c_void_p(g.view.data_ptr())  # noqa: E731
+
+
+def _tile_gemm_launch(hip, g):
+    p = g.problem(hip)[0]
+    return hip.lib.ldc_gemm_bias_act(c_void_p(p.A), c_void_p(p.W), c_void_p(p.bias), c_void_p(p.gate), c_void_p(p.R), c_void_p(p.C), byref(p.d), hip._stream())
+
+
+@pytest.mark.parametrize("K", R.TILE_GEMM_K)
+def test_tile_gemm_edges(hip, K):
+    """35 launches per depth (R.tile_gemm_shapes): staging predicated per float4 on kk < K, gm < M, gn < N with poison behind K in A AND W
+    (ldw = K + 4), behind N in C, R and the gate, and between the batches; both LDS stages at K = 64, stage 0 reused at K = 96.  The pad
+    columns of C are guard words (assert_untouched), the columns before a column offset payload that must still be UNWRITTEN."""
+    worst = 0.0
+    for M, N, K_, batch, epi in R.tile_gemm_shapes(K):
+        what = f"gemm[{TILE_PATH}] {M} x {N} x {K_}, batch {batch}, epilogue {epi}"
+        g = Gemm(hip, TILE_PATH, M, N, K_, batch, epi)
+        assert g.A.ld > K_ and g.W.ld > K_ and g.C.ld > g.col0 + N and g.A.bs > M * g.A.ld and g.C.bs > M * g.C.ld, what
+        assert (g.gate is None or g.gate.bs > N) and (g.Rbuf is None or (g.Rbuf.ld > N and g.Rbuf.bs > M * g.Rbuf.ld)), what
+        ok(_tile_gemm_launch(hip, g), what)
+        got = g.result(what)
+        want, bound = R.gemm_case_ref(M, N, K_, batch, epi, "f32")
+        r = assert_elementwise(got, want, bound, what)
+        g.new_output()
+        ok(_tile_gemm_launch(hip, g), what + ": second launch")
+        same_bits(g.result(what + ": second launch"), got, what + ": second launch")
+        note("gemm", TILE_PATH, (M, N, K_, batch, epi), r)
+        worst = max(worst, r)
+    print(f"gemm[{TILE_PATH}] K {K}: worst err / bound {worst:.3f}")
+
+
+def _refused(st, code, what, outputs, buffers):
+    assert st == code, f"{what}: status {st}, expected {code}"
+    untouched(*buffers)
+    for o in outputs:
+        still_unwritten(o.payload(), f"output of the refused call ({what})")
+
+
+def test_tile_gemm_refusals(hip):
+    """every `return` of ldc_gemm_bias_act before its launch.  The two grid-limit cases run at N = 1, K = 4 with lda = ldc = a_bs = c_bs = 0:
+    were the check wrong, every workgroup would stay inside row 0 of A and element 0 of C."""
+    M = N = K = 8
+    g = torch.Generator().manual_seed(5)
+    A, W = gin(torch.randn(1, M, K, generator=g)), gin(torch.randn(1, N, K, generator=g), gap=0)
+    C = guarded(M, N, N + 4)
+    base = dict(A=A.view.data_ptr(), W=W.view.data_ptr(), C=C.view.data_ptr(), desc=True, M=M, N=N, K=K, batch=1, lda=A.ld, ldw=W.ld, ldc=C.ld, a_bs=A.bs,
+                c_bs=C.bs, act=0, flags=0)
+
+    def call(**change):
+        a = dict(base, **change)
+        d = hip.GemmDesc(a["M"], a["N"], a["K"], a["batch"], a["lda"], a["ldw"], a["ldc"], 0, a["a_bs"], a["c_bs"], 0, 0, a["act"], a["flags"], 0)
+        return hip.lib.ldc_gemm_bias_act(c_void_p(a["A"]), c_void_p(a["W"]), None, None, None, c_void_p(a["C"]), byref(d) if a["desc"] else None, hip._stream())
+
+    one_row = dict(N=1, K=4, lda=0, ldc=0, a_bs=0, c_bs=0)
+    cases = [(dict(A=None), ERR_ARG), (dict(W=None), ERR_ARG), (dict(C=None), ERR_ARG), (dict(desc=False), ERR_ARG)]
+    cases += [({k: v}, ERR_ARG) for k in ("M", "N", "K", "batch") for v in (0, -1)]
+    cases += [(dict(A=base["A"] + 4), ERR_ALIGN), (dict(W=base["W"] + 4), ERR_ALIGN)]
+    cases += [(dict(K=6), ERR_ALIGN), (dict(lda=A.ld + 1), ERR_ALIGN), (dict(ldw=W.ld + 1), ERR_ALIGN), (dict(a_bs=A.bs + 2), ERR_ALIGN)]
+    cases += [(dict(act=-1), ERR_UNSUPPORTED), (dict(act=4), ERR_UNSUPPORTED), (dict(flags=1), ERR_UNSUPPORTED), (dict(flags=8), ERR_UNSUPPORTED)]
+    cases += [(dict(one_row, batch=65536), ERR_UNSUPPORTED), (dict(one_row, M=65535 * 128 + 1), ERR_UNSUPPORTED)]
+    for change, code in cases:
+        _refused(call(**change), code, f"ldc_gemm_bias_act with {change}", [C], [A, W, C])
+    ok(call(), "the call that every refusal above changes in one argument")
+    untouched(A, W, C)
+    want, bound = R.gemm_ref(A.payload(), W.payload()[0])
+    assert_elementwise(finite(C.payload(), "the accepted call"), want, bound, "the accepted call")
+
+
+# ---- the tile-per-workgroup kernel of gemm_f32.hip: ldc_sphere_conv_nhwc --------------------------------------------------------------
+def _tile_conv(hip, case, act, via_gather=False):
+    from ladcast_amd.models.sphere_conv import pack_dense_weight
+
+    B, H, W, cin, cout, ks, has_res = case
+    what = f"sphere conv[{TILE_PATH}] {case}, act {act}"
+    kw = R.conv_inputs(*case)
+    npix = B * H * W
+    X = gin(kw["x"].reshape(1, npix, cin), gap=0)  # ldx = cin + 4: a float4 that reaches behind cin reads poison
+    gW = gvec(pack_dense_weight(kw["w"]))  # [cout][ks * ks * cin], dense: the back guard starts behind row cout - 1
+    gb = gvec(kw["bias"])
+    Rb = gin(kw["R"].reshape(1, npix, cout), gap=0) if has_res else None
+    outs = []
+    for rep in range(2):
+        Y = guarded(npix, cout, cout + 4)
+        ok(hip.lib.ldc_sphere_conv_nhwc(VP(X), VP(gW), VP(gb), VP(Rb), VP(Y), B, H, W, cin, X.ld, cout, Y.ld, 0 if Rb is None else Rb.ld, ks, act, hip._stream()),
+           what)
+        untouched(X, gW, gb, Rb, Y)  # (the pad columns of Y are guard words)
+        outs.append(finite(Y.payload(), what).reshape(B, H, W, cout))
+    want, bound = R.conv_ref(kw["x"], kw["w"], kw["bias"], ks, "f32", act=act, R=kw["R"], via_gather=via_gather)
+    r = assert_elementwise(outs[0], want, bound, what)  # every element: both pole rows, the wrap columns and the image boundaries included
+    same_bits(outs[1], outs[0], what + ": second launch")
+    note("sphere conv", TILE_PATH, case + (act,), r)
+    return r
+
+
+@pytest.mark.parametrize("act", (0, 1))
+@pytest.mark.parametrize("case", R.TILE_CONV_CASES, ids=str)
+def test_tile_conv_edges(hip, case, act):
+    """what each case is for is written beside R.TILE_CONV_CASES"""
+    _tile_conv(hip, case, act)
+
+
+@pytest.mark.parametrize("act", (0, 1))
+def test_tile_conv_two_rows(hip, act):
+    """H = 2: the entry point accepts it, the oracle and the reference raise there.  Held to the float64 gather-GEMM over R.sphere_gather,
+    which tests/test_mfma_edge_bounds_cpu.py shows to equal the oracle conv at every H >= 3 case"""
+    _tile_conv(hip, R.TILE_CONV_H2_CASE, act, via_gather=True)
+
+
+def test_sphere_conv_module_with_padded_cin(hip):
+    """SphereConv2d(6, 5, 3, 1, 1) on (2, 6, 4, 8): cin is padded to 8 with zero weights, so columns 6 and 7 of the token buffer must BE zeros
+    (0 x NaN is NaN).  The module takes that buffer from torch.empty: the allocator is first handed freed blocks full of NaN of every size
+    the forward asks for, and the layout kernel is shown directly to zero the columns of a NaN-filled buffer."""
+    from ladcast_amd.models import SphereConv2d
+
+    B, H, W, cin, cout, ks, _ = R.MODULE_CONV_CASE
+    kw = R.conv_inputs(*R.MODULE_CONV_CASE)
+    x = kw["x"].permute(0, 3, 1, 2).contiguous().cuda()
+    tok = torch.full((B, H * W, 8), float("nan"), device="cuda")
+    hip.chan_to_token(x, tok, B=B, C=cin, N=H * W, ldo=8)
+    assert bool((tok[..., cin:] == 0).all()) and torch.equal(tok[..., :cin].cpu(), kw["x"].reshape(B, H * W, cin))
+    m = SphereConv2d(cin, cout, ks, 1, 1).cuda()
+    with torch.no_grad():
+        m.weight.copy_(kw["w"])
+        m.bias.copy_(kw["bias"])
+    torch.cuda.synchronize()
+    junk = [torch.full((n,), float("nan"), device="cuda") for n in (B * H * W * 8, B * H * W * cout, cout * ks * ks * 8) for _ in range(4)]
+    del tok, junk
+    y = m(x)
+    torch.cuda.synchronize()
+    want, bound = R.conv_ref(kw["x"], kw["w"], kw["bias"], ks, "f32")
+    got = finite(y.cpu(), "SphereConv2d(6, 5, 3)").permute(0, 2, 3, 1)
+    note("sphere conv", "SphereConv2d module", R.MODULE_CONV_CASE, assert_elementwise(got, want, bound, "SphereConv2d(6, 5, 3)"))
+
+
+def test_tile_conv_refusals(hip):
+    """every `return` of ldc_sphere_conv_nhwc before its launch but one: the pixel-count limit (B H W above 2**31 - 1, or above 65535 row
+    tiles) is NOT run here - ldx >= cin is required, so a wrongly accepted call would read gigabytes behind X on a shared machine.  It is
+    covered by reading: `M` is formed in 64 bits from the three extents, compared with 0x7fffffff and, divided by 128 and rounded up, with
+    65535, before anything is narrowed to int."""
+    B, H, W, cin, cout, ks = 1, 3, 4, 8, 8, 3
+    g = torch.Generator().manual_seed(7)
+    x, w = torch.randn(B, H, W, cin, generator=g), torch.randn(cout, cin, ks, ks, generator=g) / 8
+    X, Wt = gin(x.reshape(1, B * H * W, cin), gap=0), gvec(w.permute(0, 2, 3, 1).reshape(-1))
+    Y = guarded(B * H * W, cout, cout + 4)
+    base = dict(X=X.view.data_ptr(), Wt=Wt.view.data_ptr(), Y=Y.view.data_ptr(), B=B, H=H, W=W, cin=cin, ldx=X.ld, cout=cout, ldy=Y.ld, ksize=ks, act=0)
+
+    def call(**change):
+        a = dict(base, **change)
+        return hip.lib.ldc_sphere_conv_nhwc(c_void_p(a["X"]), c_void_p(a["Wt"]), None, None, c_void_p(a["Y"]), a["B"], a["H"], a["W"], a["cin"], a["ldx"], a["cout"],
+                                            a["ldy"], 0, a["ksize"], a["act"], hip._stream())
+
+    cases = [(dict(X=None), ERR_ARG), (dict(Wt=None), ERR_ARG), (dict(Y=None), ERR_ARG)]
+    cases += [({k: v}, ERR_ARG) for k in ("B", "H", "W", "cin", "cout") for v in (0, -2)]
+    cases += [(dict(ksize=k), ERR_UNSUPPORTED) for k in (1, 4, 7)]
+    cases += [(dict(W=3), ERR_UNSUPPORTED), (dict(H=1), ERR_UNSUPPORTED)]
+    cases += [(dict(X=base["X"] + 4), ERR_ALIGN), (dict(Wt=base["Wt"] + 4), ERR_ALIGN)]
+    cases += [(dict(cin=6), ERR_ALIGN), (dict(ldx=X.ld + 1), ERR_ALIGN), (dict(ldx=cin - 4), ERR_ALIGN), (dict(ldy=cout - 4), ERR_ALIGN)]
+    cases += [(dict(act=-1), ERR_UNSUPPORTED), (dict(act=4), ERR_UNSUPPORTED)]
+    for change, code in cases:
+        _refused(call(**change), code, f"ldc_sphere_conv_nhwc with {change}", [Y], [X, Wt, Y])
+    ok(call(), "the call that every refusal above changes in one argument")
+    untouched(X, Wt, Y)
+    want, bound = R.conv_ref(x, w, None, ks, "f32")
+    assert_elementwise(finite(Y.payload(), "the accepted call").reshape(B, H, W, cout), want, bound, "the accepted call")
