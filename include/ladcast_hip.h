@@ -843,6 +843,40 @@ int ldc_rollout_energy(const float* forecast, long long member_stride, long long
 int ldc_track_gather(const float* x, long long sb, long long st, long long sc, int B, int T, long long HW, const int* channels,
                      int n_ch, const float* mean, const float* std_, float target_std, float* out, int T_total, int t_off,
                      void* stream);
+/* Derived fields (additive under ABI 5; derive.hip): new planes computed from de-normalised channels, the
+ * sibling of ldc_track_gather.  Value (outer o, lead l, channel c, point p) of the source is
+ *   x = src[o*outer_stride + (slot ? slot[l] : l)*lead_stride + c*channel_stride + p],  o < n_outer, l < L, c < C, p < HW
+ * with a contiguous HW plane: the decoder's output (outer = member, any layout the scorers' forecast accepts), or a truth /
+ * climatology table (n_outer = 1, slot a DEVICE int array [L]; the kernel trusts the slots).  mean / std_ (device vectors [C]) and
+ * target_std de-normalise it exactly as the scorers do, (x / target_std) * std_[c] + mean[c], the division skipped for
+ * target_std == 1; mean == NULL (then std_ == NULL too): the source is physical already and its bits are taken as they are.
+ * desc: HOST array of D <= LDC_DERIVE_MAX_FIELDS fields, copied into the launch.  With a, b, c, d the de-normalised channels
+ * ch[0 .. 3] of a field (a channel may appear in several fields and twice in one):
+ *   LDC_DERIVE_DIFF   a - b, one fp32 subtraction: bit-equal to subtracting the de-normalised planes
+ *   LDC_DERIVE_SPEED  (float)sqrt((double)a*a + (double)b*b)
+ *   LDC_DERIVE_SHEAR  (float)sqrt(x*x + y*y), x = (double)a - c, y = (double)b - d
+ * in double the squares are exact and neither overflow nor underflow; the sum and the root round once each, the cast once more.  A
+ * NaN input gives NaN, inf follows IEEE.  Field k is written to out[o*out_outer_stride + l*out_lead_stride + k*out_channel_stride + p]:
+ * the tail channels of a larger tensor, or a tensor of its own.  out must not overlap the planes that are read.
+ * Every distinct source plane is read once per launch; fields are served in order, at most 16 distinct source channels per launch
+ * (D = 16 SHEAR fields of 64 different channels take four launches).  16-byte loads and stores when HW % 4 == 0 and src, out and the
+ * six strides keep 16-byte alignment; a scalar path otherwise.  No atomics, no workspace.
+ * LDC_ERR_ARG: a null src / desc / out, mean without std_ or the reverse, a non-positive size, a negative stride, D outside
+ * 1 .. LDC_DERIVE_MAX_FIELDS, an unknown kind, a channel outside 0 .. C - 1; LDC_ERR_UNSUPPORTED: L or n_outer above 65535.  Nothing is
+ * launched on an error. */
+#define LDC_DERIVE_MAX_FIELDS 16
+#define LDC_DERIVE_SPEED 0 /* ch[0 .. 1] = a, b */
+#define LDC_DERIVE_DIFF 1  /* ch[0 .. 1] = a, b */
+#define LDC_DERIVE_SHEAR 2 /* ch[0 .. 3] = a, b, c, d */
+typedef struct ldc_derive_desc {
+  int kind;
+  int ch[4]; /* indices into the C channels; entries the kind does not use are ignored */
+} ldc_derive_desc;
+int ldc_sizeof_derive_desc(void);
+int ldc_derive_fields(const float* src, long long outer_stride, long long lead_stride, long long channel_stride, const int* slot,
+                      const float* mean, const float* std_, float target_std, int n_outer, int L, int C, long long HW,
+                      const ldc_derive_desc* desc, int D, float* out, long long out_outer_stride, long long out_lead_stride,
+                      long long out_channel_stride, void* stream);
 /* out[i] = np.nanmean over e < E of x[e*member_stride + i], i < n (fp32, the reference's ds.mean(dim="idx")): NaNs skipped, the
  * sum taken in member order, one division by the count (NaN where every member is NaN). */
 int ldc_track_nanmean(const float* x, long long member_stride, int E, long long n, float* out, void* stream);

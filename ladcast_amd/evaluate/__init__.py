@@ -8,10 +8,11 @@ _VALIDATE_NAMES = ("NpyLatentStore", "log_validation", "validate_initial_time") 
 _DENOISE_NAMES = ("denoising_loss", "evaluate_denoising_loss", "push_forward_plan")  # denoise_loss's, likewise
 _PRODUCTS_NAMES = ("products_of_latent_rollout",)  # products', likewise
 _ENERGY_NAMES = ("ENERGY_NAMES", "EnergyGroup", "empty_energy", "rollout_energy")  # energy's, likewise
+_DERIVED_NAMES = ("Derived", "derive_forecast", "derive_table", "derived_metadata", "parse_derived")  # derived's, likewise
 __all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
            "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores", "rollout_spectrum",  # also runs
            "validation_scores", "empty_products", "rollout_products", "EVENT_SCORE_NAMES", "Event", "empty_events", "event_scores", "rollout_events", "FSS_SCORE_NAMES", "empty_fss", "fss_scores", "rollout_fss", "NAMED_REGIONS", "REGIONAL_SCORE_NAMES",
-           "Region", "empty_regional", "region_mask", "regional_scores", "rollout_regional", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES, *_ENERGY_NAMES]  # as `python -m`
+           "Region", "empty_regional", "region_mask", "regional_scores", "rollout_regional", *_DRIVER_NAMES, *_VALIDATE_NAMES, *_DENOISE_NAMES, *_PRODUCTS_NAMES, *_ENERGY_NAMES, *_DERIVED_NAMES]  # as `python -m`
 
 
 def __getattr__(name):
@@ -35,4 +36,8 @@ def __getattr__(name):
         from . import energy
 
         return getattr(energy, name)
+    if name in _DERIVED_NAMES:
+        from . import derived
+
+        return getattr(derived, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

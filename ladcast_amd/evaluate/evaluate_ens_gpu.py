@@ -14,6 +14,8 @@ xarray / zarr are not available: `--data_path` is a .npy of raw frames (N, C, H_
 `--start_date`; `--climatology_path` a .npy (366, 4, C, H_in, W) (day of year, hour 0 / 6 / 12 / 18).  `H_in == H + 1` crops row 0,
 the south pole.  `--reliability`, `--spectrum`, `--event` / `--event_anomaly` / `--fss_scales`, `--region` / `--region_box` and `--energy` /
 `--energy_group` add metrics that are not in the reference; what each computes and writes is stated by its class in `rollout_metrics`.
+`--derive NAME speed|diff|shear CHANNEL ...` appends a derived field (`derived`: wind speed, a difference, vertical shear) to the
+channels: every array gains a row, and `derived.json` names the fields.
 Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
 members and the reference's commented-out `single_mse` are out of scope.
 """
@@ -31,7 +33,7 @@ import torch
 
 from .track import LEVELS, NUM_ATM_VARS, VARIABLE_NAMES, mean_std_from_json
 from .rollout_metrics import (ENERGY_GROUP_NAMES, ENERGY_KEYS, ENERGY_NAMES, EVENTS_KEYS, FSS_KEYS, METRICS, REGIONAL_KEYS, RELIABILITY_KEYS,  # noqa: F401
-                              SPECTRUM_KEYS, Batch, _crop_rows, parse_energy_groups, parse_events, parse_fss_scales, parse_regions, row_latitudes,
+                              SPECTRUM_KEYS, Batch, _channel_names, _crop_rows, parse_energy_groups, parse_events, parse_fss_scales, parse_regions, row_latitudes,
                               spectrum_band_weights)  # the keys and parsers are this module's names too
 from .utils import SCORE_NAMES, get_normalized_lat_weights_based_on_cos, rollout_scores
 
@@ -97,7 +99,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                          decode_batch_frames: Optional[int] = None, reliability: bool = False, spectrum: bool = False,
                          spectrum_row_weight: Optional[torch.Tensor] = None, events: Optional[Sequence] = None,
                          regions: Optional[Sequence] = None, region_mask=None, fss_radii: Optional[Sequence[int]] = None, energy: bool = False,
-                         energy_groups: Optional[Sequence] = None, energy_scales=None) -> Dict[str, torch.Tensor]:
+                         energy_groups: Optional[Sequence] = None, energy_scales=None, derived: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -112,7 +114,13 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     `reliability`, `spectrum` / `spectrum_row_weight`, `events` / `fss_radii`, `regions` / `region_mask`, `energy` / `energy_groups` /
     `energy_scales` switch on the optional metrics of `rollout_metrics.METRICS` (`Reliability`, `Spectrum`, `Events`, `Regional`,
     `Energy`: each class states its options and the keys the result gains).  Every decode batch goes through each of them, in that
-    order, while it is on the device; nothing more is decoded or kept.  Every other output is the bits of a call without it."""
+    order, while it is on the device; nothing more is decoded or kept.  Every other output is the bits of a call without it.
+
+    `derived`: a sequence of `derived.Derived(name, kind, channels)`; the D fields become channels C' .. C' + D - 1 of every result
+    and of every option that names a channel (`events`, `energy_groups`, `energy_scales`).  Each decode batch is copied into the head
+    of a (lead, ens, C' + D, H, W) buffer whose tail `derive_forecast` fills; truth and climatology become per-batch tables extended
+    the same way, the climatology of a `speed` / `shear` field NaN (so its `ens_acc` is NaN).  A field that reads `sst_channel` and an
+    anomaly event on a `speed` / `shear` field are ValueErrors.  Without `derived` not one launch or copy is added."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
 
@@ -134,9 +142,15 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
         raise ValueError(f"nothing to score in latents of shape {tuple(latents.shape)}")
     if len(truth_slots) < T or (clim is not None and len(clim_slots) < T):
         raise ValueError(f"{T} lead times need {T} truth and climatology slots")
+    fields = None
+    if derived is not None:
+        from .derived import ExtendedBatch, _field_list, check_scoring_fields, extended_scales
+
+        fields = _field_list(derived, int(torch.as_tensor(mean_tensor).numel()))
+        check_scoring_fields(fields, int(torch.as_tensor(mean_tensor).numel()), sst_channel, events)
     options = dict(reliability=reliability, spectrum=spectrum, spectrum_row_weight=spectrum_row_weight, events=events, fss_radii=fss_radii,
                    regions=regions, region_mask=region_mask, energy=energy, energy_groups=energy_groups, energy_scales=energy_scales,
-                   clim=clim, std_tensor=std_tensor)
+                   clim=clim, std_tensor=std_tensor if fields is None else extended_scales(fields, std_tensor))
     metrics = [m for m in (cls.for_rollout(options) for cls in METRICS) if m is not None]  # their options: checked before anything is decoded
     dev = encdec_model.device
     if torch.device(dev).type != "cuda":
@@ -147,6 +161,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     if clim is not None and not (isinstance(clim, torch.Tensor) and clim.is_cuda):
         clim, c_slots = _stage_planes(clim, c_slots, dev, "clim")
     mean_d, std_d = _device_vector(mean_tensor, dev), _device_vector(std_tensor, dev)
+    ext = None if fields is None else ExtendedBatch(fields, mean_d, std_d)
     lat_weight = lat_weight.to(dev, torch.float32)
     latents = latents.to(dev, torch.float32)
     for m in metrics:
@@ -157,13 +172,22 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
         nl = min(per, T - s0)
         x = latents[:, :, s0 : s0 + nl].permute(2, 0, 1, 3, 4).reshape(nl * ens, C, h, w).contiguous()  # lead-major, then member
         y = encdec_model.decode(x).sample  # (nl * ens, C', H, W), still normalised
+        if ext is None:
+            b = Batch(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, sst_channel, total,
+                      dict(lead_dim=0, mean=mean_d, std=std_d, truth_slot=t_slots[s0 : s0 + nl], l_off=s0),
+                      dict(clim=clim, clim_slots=None if clim is None else c_slots[s0 : s0 + nl]))
+        else:  # the batch, its truth and its climatology with the derived fields as tail channels; the tables' slots are 0 .. nl - 1
+            if y.shape[1] != ext.C:
+                raise ValueError(f"the decoder gives {y.shape[1]} channels, mean_tensor / std_tensor hold {ext.C}")
+            ext.buffer(per, ens, y.shape[2], y.shape[3], dev)[:nl, :, : ext.C].copy_(y.reshape(nl, ens, *y.shape[1:]))
+            b = Batch(ext.derive(nl), ext.table("truth", truth, t_slots[s0 : s0 + nl], per), lat_weight, sst_channel, total,
+                      dict(lead_dim=0, mean=ext.mean, std=ext.std, truth_slot=list(range(nl)), l_off=s0),
+                      dict(clim=None if clim is None else ext.table("clim", clim, c_slots[s0 : s0 + nl], per),
+                           clim_slots=None if clim is None else list(range(nl))))
         if scores is None:
-            scores = torch.full((5, y.shape[1], total), float("nan"), device=dev, dtype=torch.float32)
-        b = Batch(y.reshape(nl, ens, *y.shape[1:]), truth, lat_weight, sst_channel, total,
-                  dict(lead_dim=0, mean=mean_d, std=std_d, truth_slot=t_slots[s0 : s0 + nl], l_off=s0),
-                  dict(clim=clim, clim_slots=None if clim is None else c_slots[s0 : s0 + nl]))
-        rollout_scores(b.y, truth, clim, lat_weight, sst_channel, lead_dim=0, mean=mean_d, std=std_d, truth_slots=b.kw["truth_slot"],
-                       clim_slots=b.clim_kw["clim_slots"], out=scores, lead_offset=s0)
+            scores = torch.full((5, b.y.shape[2], total), float("nan"), device=dev, dtype=torch.float32)
+        rollout_scores(b.y, b.truth, b.clim_kw["clim"], lat_weight, sst_channel, lead_dim=0, mean=b.kw["mean"], std=b.kw["std"],
+                       truth_slots=b.kw["truth_slot"], clim_slots=b.clim_kw["clim_slots"], out=scores, lead_offset=s0)
         for m in metrics:
             m.run(b)
     host = scores.cpu()  # the one copy (and the one wait) of this initial time
@@ -226,6 +250,10 @@ def main(argv=None, score: Optional[Callable] = None):
     ap.add_argument("--gemm_precision", type=str, default="fp32", choices=("fp32", "bf16x3", "bf16"))
     for cls in METRICS:
         cls.add_arguments(ap)
+    ap.add_argument("--derive", nargs="+", action="append", default=[], metavar="NAME_KIND_CHANNELS",
+                    help="NAME speed|diff|shear CHANNEL [CHANNEL ...]: also score this derived field (speed: sqrt(a^2 + b^2) of channels a b; diff: a - b; "
+                         "shear: sqrt((a - c)^2 + (b - d)^2) of a b c d) as one more channel, which --event, --energy_group and the regional results then name; "
+                         "may be given several times")
     ap.add_argument("--levels", type=int, nargs="+", default=LEVELS, help="pressure levels of the atmospheric variables, in channel order (--event channel names)")
     ap.add_argument("--num_atm_vars", type=int, default=NUM_ATM_VARS, help="leading variables that have one channel per level (--event channel names)")
     args = ap.parse_args(argv)
@@ -243,6 +271,14 @@ def main(argv=None, score: Optional[Callable] = None):
         raise SystemExit(f"{args.result_path}: no latent_*.npy at or before end_date - total_lead_time_hour")
 
     metrics = [m for m in (cls.from_args(args, total_num_steps, files) for cls in METRICS) if m is not None]
+    fields = None
+    if args.derive:
+        from .derived import check_scoring_fields, derived_metadata, extended_scales, parse_derived
+
+        decoded = _channel_names(args)[: -len(args.derive)]
+        fields = parse_derived(args.derive, decoded)
+        check_scoring_fields(fields, len(decoded), args.sst_channel_idx, [ev for m in metrics for ev in getattr(m, "events", ())])
+        derived_meta = derived_metadata(fields, decoded)
 
     if score is None:
         if args.encdec_model is None or args.data_path is None or args.climatology_path is None:
@@ -264,8 +300,13 @@ def main(argv=None, score: Optional[Callable] = None):
             clim = torch.from_numpy(np.ascontiguousarray(clim, dtype=np.float32)).to("cuda")
         lat_w = lat_weights_for(H)
         kw = {}
+        std_ext = std_t
+        if fields is not None:
+            kw["derived"] = fields
+            derived_meta = derived_metadata(fields, decoded, std_t)
+            std_ext = extended_scales(fields, std_t)
         for m in metrics:
-            kw.update(m.rollout_kwargs(H, int(truth.shape[-1]), lat_w, std_t))
+            kw.update(m.rollout_kwargs(H, int(truth.shape[-1]), lat_w, std_ext))
 
         def score(path, time_str, t_slots, c_slots):
             return score_latent_rollout(path, model, mean_t, std_t, truth, t_slots, clim, c_slots, lat_w, sst_channel=args.sst_channel_idx,
@@ -290,6 +331,9 @@ def main(argv=None, score: Optional[Callable] = None):
     out = {k: np.stack(v) for k, v in gathered.items()}
     for m in metrics:
         m.finish(out, args.output)
+    if fields is not None:
+        with open(os.path.join(args.output, "derived.json"), "w") as f:
+            json.dump(dict(decoded_channels=len(decoded), derived=derived_meta), f, indent=1)
     out["timestamp"] = np.array([int(t) for t, _ in files]).astype(np.float32)  # as the reference: a float32 tensor of YYYYMMDDHH
     for k, a in out.items():
         np.save(os.path.join(args.output, f"{k}.npy"), a)

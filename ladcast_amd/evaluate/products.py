@@ -14,7 +14,9 @@ the ensemble size - are all that leaves the device.  Decoded fields never exist 
 Channels are named as `validate_AR.column_names(track.VARIABLE_NAMES)` names them (`geopotential_level500`, `2m_temperature`, ...) or by
 index.  Per `latent_YYYYMMDDHH.npy` one `products_YYYYMMDDHH.npz` with `mean`, `std`, `min`, `max` (Cs, lead time, H, W), `quantiles`
 (Q, Cs, lead time, H, W) and `exceed` (P, Cs, lead time, H, W), and one `products.json` with the channel names, the quantiles, the
-thresholds with their direction and the ensemble size.  A threshold applies to its one channel: the other channels of that `exceed`
+thresholds with their direction and the ensemble size.  `--derive NAME speed|diff|shear CHANNEL ...` adds a derived field (`derived`) as one
+more channel - `--derive wind_speed_10m speed 10m_u_component_of_wind 10m_v_component_of_wind --exceed wind_speed_10m gt 17.2` maps the
+probability of gale-force wind - and `products.json` gains `derived`.  A threshold applies to its one channel: the other channels of that `exceed`
 plane hold NaN.  Single rank; `.npy` / `.npz` only.
 """
 from __future__ import annotations
@@ -39,7 +41,7 @@ DIRECTIONS = {"gt": 1, "lt": -1}
 def products_of_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model, mean_tensor, std_tensor, *, quantiles: Sequence[float] = (),
                                thresholds=None, threshold_dirs: Optional[Sequence[int]] = None, channels: Optional[Sequence[int]] = None,
                                total_num_steps: Optional[int] = None, crop_init: bool = False, force_ens_size: Optional[int] = None,
-                               decode_batch_frames: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                               decode_batch_frames: Optional[int] = None, derived: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
     """One initial time: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> fp32 CPU tensors `mean`, `std`, `min`, `max`
     (Cs, total_num_steps, H, W), and with quantiles / thresholds `quantiles` (Q, Cs, total_num_steps, H, W) / `exceed` (P, Cs,
     total_num_steps, H, W), in physical units (`mean_tensor` / `std_tensor`: one value per decoded channel).
@@ -51,7 +53,11 @@ def products_of_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec
     bits, and a performance setting must not move a forecast product.  With decoder calls of one fixed size the products hold the same
     bits under every `decode_batch_frames`.  `quantiles`, `thresholds` (P, Cs), `threshold_dirs`, `channels`: as `rollout_products`.
     Columns T .. total_num_steps - 1 stay NaN; T > total_num_steps is a ValueError.  `crop_init` drops slot 0 (the IC latent),
-    `force_ens_size` keeps the first members."""
+    `force_ens_size` keeps the first members.
+
+    `derived`: a sequence of `derived.Derived(name, kind, channels)`; the D fields become channels C' .. C' + D - 1, which `channels`
+    and the columns of `thresholds` then address like any other: every decode batch is assembled in a (lead, ens, C' + D, H, W) buffer
+    whose tail `derive_forecast` fills in physical units.  The products of the decoded channels keep their bits."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
 
@@ -75,6 +81,11 @@ def products_of_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec
     if torch.device(dev).type != "cuda":
         raise RuntimeError("ladcast_amd products need the model on the device (no CPU fallback)")
     mean_d, std_d = _device_vector(mean_tensor, dev), _device_vector(std_tensor, dev)
+    ext = None
+    if derived is not None:
+        from .derived import ExtendedBatch
+
+        ext = ExtendedBatch(derived, mean_d, std_d)
     latents = latents.to(dev, torch.float32)
     quantiles = list(quantiles)
     thr_d = None if thresholds is None else torch.as_tensor(thresholds, dtype=torch.float32).to(dev)
@@ -84,18 +95,25 @@ def products_of_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec
         nl = min(per, T - s0)
         for k in range(nl):  # one decoder call per lead time, always `ens` frames: the same schedule, so the same bits, under every batch size
             yk = encdec_model.decode(latents[:, :, s0 + k].contiguous()).sample  # (ens, C', H, W), still normalised
+            if ext is not None:  # the batch is assembled in the head channels of the extended buffer
+                if yk.shape[1] != ext.C:
+                    raise ValueError(f"the decoder gives {yk.shape[1]} channels, mean_tensor / std_tensor hold {ext.C}")
+                ext.buffer(per, ens, yk.shape[2], yk.shape[3], dev)[k, :, : ext.C].copy_(yk)
+                continue
             if nl == 1:
                 y = yk.unsqueeze(0)
                 break
             if y is None or y.shape[0] < nl:
                 y = torch.empty(per, *yk.shape, device=dev, dtype=torch.float32)  # the decode batch, lead-major: (lead, ens, C', H, W)
             y[k].copy_(yk)
+        if ext is not None:
+            y = ext.derive(nl)
         if prod is None:
             Cs = y.shape[2] if channels is None else len(channels)
             prod = empty_products(Cs, total, y.shape[3], y.shape[4], dev, n_quantiles=len(quantiles),
                                   n_thresholds=0 if thr_d is None else thr_d.shape[0])
         rollout_products(y[:nl], quantiles=quantiles, thresholds=thr_d, threshold_dirs=threshold_dirs, channels=channels, lead_dim=0,
-                         mean=mean_d, std=std_d, out=prod, l_off=s0)
+                         mean=mean_d if ext is None else ext.mean, std=std_d if ext is None else ext.std, out=prod, l_off=s0)
     return {k: v.cpu() for k, v in prod.items()}
 
 
@@ -144,6 +162,9 @@ def main(argv=None, products: Optional[Callable] = None):
     ap.add_argument("--quantiles", type=float, nargs="*", default=[], help=f"up to {MAX_PRODUCT_QUANTILES} values in [0, 1]")
     ap.add_argument("--exceed", nargs=3, action="append", default=[], metavar=("CHANNEL", "gt|lt", "VALUE"),
                     help=f"probability that CHANNEL is above (gt) / below (lt) VALUE, in physical units; up to {MAX_PRODUCT_THRESHOLDS} times")
+    ap.add_argument("--derive", nargs="+", action="append", default=[], metavar="NAME_KIND_CHANNELS",
+                    help="NAME speed|diff|shear CHANNEL [CHANNEL ...]: a derived field (wind speed sqrt(a^2 + b^2), difference a - b, shear sqrt((a - c)^2 + (b - d)^2)) "
+                         "as one more channel, which --channels and --exceed then name; may be given several times")
     ap.add_argument("--total_num_steps", type=int, default=None, help="lead-time columns of the products (default: those of each file)")
     ap.add_argument("--crop_init", action="store_true", help="drop slot 0 of the latents (the initial condition)")
     ap.add_argument("--force_ens_size", type=int, default=None, help="use the first members only")
@@ -155,6 +176,14 @@ def main(argv=None, products: Optional[Callable] = None):
     args = ap.parse_args(argv)
 
     names = column_names(args.variable_names, args.levels, args.num_atm_vars)
+    fields, derived_meta = None, []
+    if args.derive:
+        from .derived import derived_metadata, parse_derived
+
+        decoded = names
+        fields = parse_derived(args.derive, decoded)
+        derived_meta = derived_metadata(fields, decoded)
+        names = decoded + [f.name for f in fields]
     channels = list(range(len(names))) if args.channels is None else resolve_channels(args.channels, names)
     if len(args.quantiles) > MAX_PRODUCT_QUANTILES or any(not 0.0 <= q <= 1.0 for q in args.quantiles):
         raise ValueError(f"--quantiles: up to {MAX_PRODUCT_QUANTILES} values in [0, 1]")
@@ -175,6 +204,8 @@ def main(argv=None, products: Optional[Callable] = None):
 
         with open(args.normalization_json) as f:
             mean_t, std_t = mean_std_from_json(json.load(f), args.variable_names)
+        if fields is not None:
+            derived_meta = derived_metadata(fields, decoded, std_t)
         model = _load_encdec(args.encdec_model).to("cuda").eval()
         model.set_gemm_precision(args.gemm_precision)
 
@@ -182,7 +213,7 @@ def main(argv=None, products: Optional[Callable] = None):
             return products_of_latent_rollout(path, model, mean_t, std_t, quantiles=args.quantiles, thresholds=thr, threshold_dirs=dirs,
                                               channels=None if args.channels is None else channels, total_num_steps=args.total_num_steps,
                                               crop_init=args.crop_init, force_ens_size=args.force_ens_size,
-                                              decode_batch_frames=args.decode_batch_frames)
+                                              decode_batch_frames=args.decode_batch_frames, derived=fields)
 
     os.makedirs(args.output, exist_ok=True)
     ens_size = None
@@ -202,6 +233,8 @@ def main(argv=None, products: Optional[Callable] = None):
         ens_size = n
     meta = dict(channels=[names[c] for c in channels], channel_indices=channels, quantiles=[float(q) for q in args.quantiles],
                 thresholds=thr_meta, ensemble_size=int(ens_size), init_times=[t for t, _ in files])
+    if fields is not None:
+        meta["derived"] = derived_meta
     with open(os.path.join(args.output, "products.json"), "w") as f:
         json.dump(meta, f, indent=1)
     print(f"saved products of {len(files)} initial times x {len(channels)} channels to {args.output}")

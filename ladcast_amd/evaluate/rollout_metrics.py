@@ -57,7 +57,12 @@ def _crop_rows(table: np.ndarray, H: int, what: str) -> np.ndarray:
 def _channel_names(args) -> List[str]:  # the names `--event` and `--energy_group` resolve a CHANNEL against
     from .validate_AR import column_names
 
-    return column_names(args.variable_names, args.levels, args.num_atm_vars)
+    names = column_names(args.variable_names, args.levels, args.num_atm_vars)
+    if getattr(args, "derive", None):  # the derived fields are channels C', C' + 1, ... of everything
+        from .derived import parse_derived
+
+        names = names + [d.name for d in parse_derived(args.derive, names)]
+    return names
 
 
 class Metric:

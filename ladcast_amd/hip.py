@@ -67,6 +67,15 @@ EVENTS_MAX, EVENTS_MAX_MEMBERS = 32, 1024  # LDC_EVENTS_MAX, the largest ensembl
 FSS_SCALES_MAX, FSS_SUMS = 16, 6  # LDC_FSS_SCALES_MAX, the sums per (event, radius, lead time) of ldc_rollout_fss
 
 
+DERIVE_MAX_FIELDS = 16  # LDC_DERIVE_MAX_FIELDS
+DERIVE_SPEED, DERIVE_DIFF, DERIVE_SHEAR = 0, 1, 2  # LDC_DERIVE_*
+DERIVE_INPUTS = {DERIVE_SPEED: 2, DERIVE_DIFF: 2, DERIVE_SHEAR: 4}  # source channels per kind
+
+
+class DeriveDesc(Structure):  # ldc_derive_desc
+    _fields_ = [("kind", c_int), ("ch", c_int * 4)]
+
+
 class EventsDesc(Structure):  # ldc_events_desc
     _fields_ = [("n_events", c_int), ("channel", c_int * EVENTS_MAX), ("dir", c_int * EVENTS_MAX), ("anomaly", c_int * EVENTS_MAX),
                 ("thr", c_float * EVENTS_MAX)]
@@ -178,6 +187,8 @@ def _load():
         "ldc_pixel_shuffle_shortcut": (I, [P, P, P, I, I, I, I, I, P]),
         "ldc_chan_regroup": (I, [P, P, L, I, I, P]),
         "ldc_track_gather": (I, [P, L, L, L, I, I, L, POINTER(c_int), I, P, P, F, P, I, I, P]),
+        "ldc_sizeof_derive_desc": (I, []),
+        "ldc_derive_fields": (I, [P, L, L, L, P, P, P, F, I, I, I, L, POINTER(DeriveDesc), I, P, L, L, L, P]),
         "ldc_track_nanmean": (I, [P, L, I, L, P, P]),
         "ldc_track_storms": (I, [P, L, L, L, L, P, P, I, P, I, P, P, I, I, POINTER(c_int), I, I, P, P, P, P]),
         "ldc_track_local_min": (I, [P, L, P, P, I, P, I, P, P, P, I, P, P, P, P, P]),
@@ -201,6 +212,8 @@ def _load():
         raise RuntimeError("ldc_products_desc layout mismatch between header and binding")
     if lib.ldc_sizeof_events_desc() != ctypes.sizeof(EventsDesc):
         raise RuntimeError("ldc_events_desc layout mismatch between header and binding")
+    if lib.ldc_sizeof_derive_desc() != ctypes.sizeof(DeriveDesc):
+        raise RuntimeError("ldc_derive_desc layout mismatch between header and binding")
     return lib, sig
 
 
@@ -837,6 +850,31 @@ def track_gather(x, out, channels, mean, std, *, sb, st, sc, B, T, HW, T_total, 
     _dev(x, out, mean, std)
     _check(lib.ldc_track_gather(_p(x), sb, st, sc, B, T, HW, _int_array(channels), len(channels), _p(mean), _p(std), float(target_std),
                                 _p(out), T_total, t_off, _stream()), "ldc_track_gather")
+
+
+def derive_desc(fields):
+    """the ldc_derive_desc array for a sequence of (kind, channels): kind one of DERIVE_*, as many channels as `DERIVE_INPUTS` states.
+    Host only; the channel range is checked by the caller, who knows C."""
+    fs = [(int(k), [int(c) for c in ch]) for k, ch in fields]
+    if not 1 <= len(fs) <= DERIVE_MAX_FIELDS:
+        raise ValueError(f"{len(fs)} derived fields: ldc_derive_fields takes 1 .. {DERIVE_MAX_FIELDS} per call")
+    arr = (DeriveDesc * len(fs))()
+    for d, (kind, ch) in zip(arr, fs):
+        if kind not in DERIVE_INPUTS or len(ch) != DERIVE_INPUTS[kind]:
+            raise ValueError(f"derived field (kind {kind}, channels {ch}): kind {DERIVE_SPEED} / {DERIVE_DIFF} reads 2 channels, {DERIVE_SHEAR} reads 4")
+        d.kind = kind
+        for j, c in enumerate(ch):
+            d.ch[j] = c
+    return arr
+
+
+def derive_fields(src, out, desc, *, outer_stride, lead_stride, channel_stride, n_outer, L, C, HW, out_outer_stride, out_lead_stride,
+                  out_channel_stride, slot=None, mean=None, std=None, target_std=1.0):
+    """out[o][l][k] = field k of `desc` (`derive_desc`) computed from the inverse-normalised channels of src (ladcast_hip.h:
+    ldc_derive_fields); slot: device int32 [L] or None; the three out strides place the planes"""
+    _dev(src, out, slot, mean, std)
+    _check(lib.ldc_derive_fields(_p(src), outer_stride, lead_stride, channel_stride, _p(slot), _p(mean), _p(std), float(target_std), n_outer, L, C,
+                                 HW, desc, len(desc), _p(out), out_outer_stride, out_lead_stride, out_channel_stride, _stream()), "ldc_derive_fields")
 
 
 def track_nanmean(x, out, *, member_stride, E, n):
