@@ -84,16 +84,8 @@ __host__ inline WsLayout ws_layout(const Geo& g, int C, int L, int nchunk) {
 }
 
 struct EnArgs {
-  const float* fc;
-  const float* truth;
-  const float* lat_w;  // [H]
-  const int* tr_slot;  // [L]
-  const float* mean;   // [C] or nullptr (forecast already in physical units)
-  const float* sd;     // [C]
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs;
-  int M, C, H, W;
-  double* part;     // [L][C][nchunk][NBP][16]
+  RolloutView v;    // no climatology
+  double* part;    // [L][C][nchunk][NBP][16]
   double* wv_part;  // [L][C][nchunk]
   int* ninv_part;   // [L][C][nchunk]
   int ntile, nchunk;
@@ -109,11 +101,11 @@ __global__ __launch_bounds__(TPB) void energy_pair_kernel(EnArgs a) {
   __shared__ int s_cnt[PT];
   __shared__ unsigned char s_nan[NVG][PT];
   float* s_y = reinterpret_cast<float*>(s_buf);
-  const Geo g = make_geo(a.M);
+  const Geo g = make_geo(a.v.M);
   const int c = blockIdx.y, l = blockIdx.z;
   const int chunk = blockIdx.x / g.NGRP, grp = blockIdx.x % g.NGRP;
-  const int M = a.M, N = g.N, RS = g.RS;
-  const int HW = a.H * a.W;
+  const int M = a.v.M, N = g.N, RS = g.RS;
+  const int HW = a.v.H * a.v.W;
   const int tid = threadIdx.x;
   const int sp = tid & (PT - 1), vg = tid / PT;
   const int s = tid / g.BPG, bpl = tid % g.BPG;
@@ -128,10 +120,9 @@ __global__ __launch_bounds__(TPB) void energy_pair_kernel(EnArgs a) {
     }
     bj = bi + rem;
   }
-  const float* fbase = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs;
-  const float* tbase = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
+  const float* fbase = view_forecast(a.v, c, l);
+  const float* tbase = view_truth(a.v, c, l);
+  const InvNorm nrm = view_norm<INV>(a.v, c);
   for (int i = N + vg; i < RS; i += NVG) s_y[sp * RS + i] = 0.f;  // the columns behind the truth: never written again
   double acc[4][4];
 #pragma unroll
@@ -148,14 +139,7 @@ __global__ __launch_bounds__(TPB) void energy_pair_kernel(EnArgs a) {
     bool nan = false;
     for (int i = vg; i < N; i += NVG) {
       float v = 0.f;
-      if (inb) {
-        if (i < M) {
-          v = fbase[static_cast<long long>(i) * a.fc_ms + p];
-          if constexpr (INV) v = inv_norm(v, nrm);
-        } else {
-          v = tbase[p];
-        }
-      }
+      if (inb) v = i < M ? load_member<INV>(fbase + p, i, a.v.fc_ms, nrm) : tbase[p];
       nan = nan || (v != v);
       s_y[sp * RS + i] = v;
     }
@@ -167,7 +151,7 @@ __global__ __launch_bounds__(TPB) void energy_pair_kernel(EnArgs a) {
     if (bad)  // replaced, not multiplied by zero: the point adds +0.0 to every sum
       for (int i = vg; i < N; i += NVG) s_y[sp * RS + i] = 0.f;
     if (vg == 0) {
-      s_w[sp] = bad ? 0.0 : static_cast<double>(a.lat_w[p / a.W]);
+      s_w[sp] = bad ? 0.0 : static_cast<double>(a.v.lat_w[p / a.v.W]);
       n_inv += (bad && inb) ? 1 : 0;
     }
     __syncthreads();
@@ -198,7 +182,7 @@ __global__ __launch_bounds__(TPB) void energy_pair_kernel(EnArgs a) {
   double* s_red = s_buf;
   if (active && bp == 0) s_wred[s] = wacc;
   if (vg == 0) s_cnt[sp] = n_inv;
-  const long long rec = (static_cast<long long>(l) * a.C + c) * a.nchunk + chunk;
+  const long long rec = (static_cast<long long>(l) * a.v.C + c) * a.nchunk + chunk;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -379,14 +363,13 @@ extern "C" int ldc_rollout_energy(const float* forecast, long long member_stride
                                   const double* inv_scale2, int G, int M, int C, int L, int H, int W, double* energy, double* energy_group,
                                   int* n_invalid, double* dist2, int L_total, int l_off, void* workspace, long long workspace_bytes,
                                   void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(lat_weight);
+  EnArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, nullptr, 0, 0, nullptr, lat_weight, M, C, L, H, W, L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(energy);
   LDC_CHECK_PTR(n_invalid);
   LDC_CHECK_PTR(workspace);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (G < 0) return LDC_ERR_ARG;
   if (G > 0) {
     LDC_CHECK_PTR(group_mask);
@@ -401,17 +384,6 @@ extern "C" int ldc_rollout_energy(const float* forecast, long long member_stride
   if (misaligned(workspace) || misaligned(energy) || misaligned(energy_group) || misaligned(dist2) || misaligned(inv_scale2))
     return LDC_ERR_ALIGN;
   const Geo g = make_geo(M);
-  EnArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.lat_w = lat_weight;
-  a.tr_slot = truth_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.M = M; a.C = C; a.H = H; a.W = W;
   a.ntile = ldc_cdiv(static_cast<long long>(H) * W, PT);
   a.nchunk = ldc_cdiv(a.ntile, CHUNK_TILES);
   const WsLayout w = ws_layout(g, C, L, a.nchunk);

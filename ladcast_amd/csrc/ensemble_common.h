@@ -1,6 +1,8 @@
-// Shared by the ensemble-statistics kernels (scoring.hip, reliability.hip, spectrum.hip, products.hip): the fused inverse normalisation,
-// the register sort with its (NP, NUSE) ladder over the ensemble size, and the argument checks of the entry points that address a forecast
-// by member / lead / channel strides.
+// Shared by the ensemble-statistics kernels (scoring.hip, reliability.hip, spectrum.hip, products.hip, regional.hip, energy.hip and, through
+// events_common.h, events.hip and fss.hip): the fused inverse normalisation, the register sort with its (NP, NUSE) ladder over the ensemble
+// size, the members-in-registers ladder, and RolloutView - how the nine entry points that read a decoded rollout (ldc_rollout_scores,
+// ldc_validation_scores, ldc_rollout_reliability / _spectrum / _products / _events / _fss / _regional / _energy) address a forecast, its truth
+// and its climatology, with the one host function that checks and fills it.  ldc_ensemble_scores (one lead time, no slots) keeps its own.
 #pragma once
 #include <type_traits>
 
@@ -66,12 +68,79 @@ static inline void ldc_dispatch_sort_arm(int M, F&& f) {
   else f(integral_constant<int, 64>{}, integral_constant<int, 64>{});
 }
 
-// What ldc_rollout_scores, ldc_validation_scores, ldc_rollout_reliability, ldc_rollout_spectrum and ldc_rollout_products ask of a forecast
-// (M, C, L, H, W) written to columns l_off .. l_off + L - 1 of L_total, and of its inverse normalisation: LDC_OK or LDC_ERR_ARG.  Pointer
-// checks and limits of its own (LDC_ERR_UNSUPPORTED) stay with each entry point.
-static inline int ldc_check_forecast_args(int M, int C, int L, int H, int W, int L_total, int l_off, const float* mean, const float* std_) {
+// The members-in-registers arm that serves M members: NMAX = 8 / 16 / 32 / 64 registers with compile-time indices, or 0 = any M, streamed.
+// Calls f(integral_constant<NMAX>), from which the caller launches its kernel<NMAX>.
+template <class F>
+static inline void ldc_dispatch_member_arm(int M, F&& f) {
+  using std::integral_constant;
+  if (M <= 8) f(integral_constant<int, 8>{});
+  else if (M <= 16) f(integral_constant<int, 16>{});
+  else if (M <= 32) f(integral_constant<int, 32>{});
+  else if (M <= 64) f(integral_constant<int, 64>{});
+  else f(integral_constant<int, 0>{});
+}
+
+// A decoded rollout as every rollout entry point reads it: the forecast (M, C, L, H, W) by member / lead / channel strides with a contiguous
+// (H, W) plane (the (ens, C, T, H, W) array or the decoder's frame-major (L * ens, C, H, W) output), truth and climatology as tables of
+// planes with a slot per lead time, the optional inverse normalisation.  The first member of each kernel's argument struct.
+struct RolloutView {
+  const float* fc;
+  const float* truth;  // nullptr: the entry point has no truth (products)
+  const float* clim;   // nullptr: none
+  const float* lat_w;  // [H]
+  const int* tr_slot;  // [L]
+  const int* cl_slot;  // [L]
+  const float* mean;   // [C] or nullptr (forecast already in physical units)
+  const float* sd;     // [C]
+  float target_std;
+  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs, cl_ss, cl_cs;  // elements
+  int M, C, H, W;
+};
+
+// Plane (channel c, lead time l): member 0 of the forecast, the truth, the climatology (nullptr without one).
+__device__ __forceinline__ const float* view_forecast(const RolloutView& v, int c, int l) {
+  return v.fc + static_cast<long long>(l) * v.fc_ls + static_cast<long long>(c) * v.fc_cs;
+}
+__device__ __forceinline__ const float* view_truth(const RolloutView& v, int c, int l) {
+  return v.truth + static_cast<long long>(v.tr_slot[l]) * v.tr_ss + static_cast<long long>(c) * v.tr_cs;
+}
+__device__ __forceinline__ const float* view_clim(const RolloutView& v, int c, int l) {
+  return v.clim ? v.clim + static_cast<long long>(v.cl_slot[l]) * v.cl_ss + static_cast<long long>(c) * v.cl_cs : nullptr;
+}
+template <bool INV>
+__device__ __forceinline__ InvNorm view_norm(const RolloutView& v, int c) {
+  if constexpr (INV) return make_inv_norm(v.target_std, v.sd, v.mean, c);
+  else return InvNorm{};
+}
+// Member i of the point f points at (member 0), after the inverse normalisation.
+template <bool INV>
+__device__ __forceinline__ float load_member(const float* f, int i, long long fc_ms, const InvNorm& nrm) {
+  float v = f[static_cast<long long>(i) * fc_ms];
+  if constexpr (INV) v = inv_norm(v, nrm);
+  return v;
+}
+
+// Checks and fills the view from the leading C arguments of a rollout entry point, in ABI order, for a forecast written to columns
+// l_off .. l_off + L - 1 of L_total: LDC_OK or LDC_ERR_ARG.  Entry points without a climatology pass nullptr, 0, 0, nullptr; with_truth =
+// false (products) also waives truth, truth_slot and lat_weight.  Pointer checks and limits of its own (LDC_ERR_UNSUPPORTED) stay with each
+// entry point, behind this call.
+static inline int ldc_rollout_view(RolloutView* v, const float* forecast, long long member_stride, long long lead_stride,
+                                   long long channel_stride, const float* mean, const float* std_, float target_std, const float* truth,
+                                   long long truth_slot_stride, long long truth_channel_stride, const int* truth_slot, const float* clim,
+                                   long long clim_slot_stride, long long clim_channel_stride, const int* clim_slot, const float* lat_weight,
+                                   int M, int C, int L, int H, int W, int L_total, int l_off, bool with_truth = true) {
+  LDC_CHECK_PTR(forecast);
+  if (with_truth) {
+    LDC_CHECK_PTR(truth);
+    LDC_CHECK_PTR(truth_slot);
+    LDC_CHECK_PTR(lat_weight);
+  }
+  if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
   if (mean != nullptr && std_ == nullptr) return LDC_ERR_ARG;
   if (M <= 0 || C <= 0 || L <= 0 || H <= 0 || W <= 0 || L_total <= 0 || l_off < 0) return LDC_ERR_ARG;
   if (static_cast<long long>(l_off) + L > L_total) return LDC_ERR_ARG;
+  *v = RolloutView{forecast, truth, clim, lat_weight, truth_slot, clim_slot, mean, std_, target_std,
+                   member_stride, lead_stride, channel_stride, truth_slot_stride, truth_channel_stride, clim_slot_stride, clim_channel_stride,
+                   M, C, H, W};
   return LDC_OK;
 }

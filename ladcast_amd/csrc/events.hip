@@ -38,19 +38,9 @@ constexpr int n_bins(int M) { return 2 * (M + 1); }
 constexpr int rec_words(int M) { return HEAD + 2 * n_bins(M); }
 
 struct EvArgs {
-  const float* fc;
-  const float* truth;
-  const float* clim;   // nullptr: no anomaly event
-  const float* lat_w;  // [H]
-  const int* tr_slot;  // [L]
-  const int* cl_slot;  // [L]
-  const float* mean;   // [C] or nullptr (forecast already in physical units)
-  const float* sd;     // [C]
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs, cl_ss, cl_cs;
-  int M, E, H, W;
+  RolloutView v;   // clim nullptr: no anomaly event
   unsigned* part;  // [L][E][nrec][rec_words(M)]
-  int ntile, tpw, nrec;
+  int E, ntile, tpw, nrec;
   ldc_events_desc d;
 };
 
@@ -60,17 +50,16 @@ template <int NMAX, bool INV, int DIR>
 __device__ __forceinline__ void events_body(const EvArgs& a, int* s_key, float* s_w, int* red_i) {
   constexpr int KB = NMAX > 0 ? 1 : KB_MAX;
   const int e = blockIdx.y, l = blockIdx.z;
-  const int M = a.M;
-  const int HW = a.H * a.W;
+  const int M = a.v.M;
+  const int HW = a.v.H * a.v.W;
   const int tid = threadIdx.x;
   const int c = a.d.channel[e];
   const float thr = a.d.thr[e];
   const bool anom = a.d.anomaly[e] != 0;
-  const float* fbase = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs;
-  const float* tbase = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs;
-  const float* cbase = anom ? a.clim + static_cast<long long>(a.cl_slot[l]) * a.cl_ss + static_cast<long long>(c) * a.cl_cs : nullptr;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
+  const float* fbase = view_forecast(a.v, c, l);
+  const float* tbase = view_truth(a.v, c, l);
+  const float* cbase = anom ? view_clim(a.v, c, l) : nullptr;
+  const InvNorm nrm = view_norm<INV>(a.v, c);
   const int nk = (n_bins(M) + TPB - 1) / TPB;  // bin slots per thread in use: workgroup-uniform
   int n_inv = 0;
   int hc[KB];
@@ -88,9 +77,9 @@ __device__ __forceinline__ void events_body(const EvArgs& a, int* s_key, float* 
     const int pp = in ? p : 0;
     const float* f = fbase + pp;
     const float t = tbase[pp];
-    const float w = a.lat_w[pp / a.W];
+    const float w = a.v.lat_w[pp / a.v.W];
     const float cl = anom ? cbase[pp] : 0.f;
-    const EventPoint pt = classify_event_point<NMAX, INV, DIR>(f, a.fc_ms, M, t, cl, anom, thr, nrm);
+    const EventPoint pt = classify_event_point<NMAX, INV, DIR>(f, a.v.fc_ms, M, t, cl, anom, thr, nrm);
     const int n = pt.n, o = pt.o;
     const bool valid = in && pt.valid;
     n_inv += (in && !valid) ? 1 : 0;
@@ -178,12 +167,9 @@ __global__ __launch_bounds__(TPB) void events_finish_kernel(const unsigned* __re
 
 template <bool INV>
 void launch_events(const EvArgs& a, dim3 grid, hipStream_t s) {
-  const int M = a.M;
-  if (M <= 8) hipLaunchKernelGGL((events_kernel<8, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 16) hipLaunchKernelGGL((events_kernel<16, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 32) hipLaunchKernelGGL((events_kernel<32, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 64) hipLaunchKernelGGL((events_kernel<64, INV>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((events_kernel<0, INV>), grid, dim3(TPB), 0, s, a);
+  ldc_dispatch_member_arm(a.v.M, [&](auto nmax) {
+    hipLaunchKernelGGL((events_kernel<decltype(nmax)::value, INV>), grid, dim3(TPB), 0, s, a);
+  });
 }
 
 }  // namespace
@@ -204,17 +190,16 @@ extern "C" int ldc_rollout_events(const float* forecast, long long member_stride
                                   long long clim_channel_stride, const int* clim_slot, const float* lat_weight, int M, int C, int L, int H,
                                   int W, const ldc_events_desc* desc, int* hist_count, float* hist_weight, int* n_invalid, int L_total,
                                   int l_off, void* workspace, long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(lat_weight);
+  EvArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, clim, clim_slot_stride, clim_channel_stride, clim_slot, lat_weight, M, C, L, H, W,
+                       L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(desc);
   LDC_CHECK_PTR(hist_count);
   LDC_CHECK_PTR(hist_weight);
   LDC_CHECK_PTR(n_invalid);
   LDC_CHECK_PTR(workspace);
-  if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   const int E = desc->n_events;
   if (E < 1 || E > LDC_EVENTS_MAX) return LDC_ERR_ARG;
   for (int e = 0; e < E; ++e) {
@@ -226,20 +211,7 @@ extern "C" int ldc_rollout_events(const float* forecast, long long member_stride
   }
   if (M > MAX_M || L > 65535 || static_cast<long long>(H) * W > (1ll << 24)) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_events_workspace_bytes(M, E, L, H, W)) return LDC_ERR_ARG;
-  EvArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.clim = clim;
-  a.lat_w = lat_weight;
-  a.tr_slot = truth_slot;
-  a.cl_slot = clim_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.cl_ss = clim_slot_stride; a.cl_cs = clim_channel_stride;
-  a.M = M; a.E = E; a.H = H; a.W = W;
+  a.E = E;
   a.part = static_cast<unsigned*>(workspace);
   a.ntile = ldc_cdiv(static_cast<long long>(H) * W, TPB);
   a.tpw = tiles_per_wg(M);

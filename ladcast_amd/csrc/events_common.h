@@ -29,7 +29,7 @@ __device__ __forceinline__ EventPoint classify_event_point(const float* f, long 
   if constexpr (NMAX > 0) {
     float x[NX];
 #pragma unroll
-    for (int i = 0; i < NX; ++i) x[i] = i < M ? f[static_cast<long long>(i) * fc_ms] : 0.f;
+    for (int i = 0; i < NX; ++i) x[i] = i < M ? load_member<false>(f, i, fc_ms, nrm) : 0.f;  // every load issued before a value is used
 #pragma unroll
     for (int i = 0; i < NX; ++i)
       if (i < M) {
@@ -41,8 +41,7 @@ __device__ __forceinline__ EventPoint classify_event_point(const float* f, long 
       }
   } else {
     for (int i = 0; i < M; ++i) {
-      float v = f[static_cast<long long>(i) * fc_ms];
-      if constexpr (INV) v = inv_norm(v, nrm);
+      const float v = load_member<INV>(f, i, fc_ms, nrm);
       nan_m = nan_m || (v != v);
       const float u = anom ? v - cl : v;
       n += hit<DIR>(u, thr);

@@ -41,17 +41,8 @@ __device__ __forceinline__ Sat operator+(const Sat& a, const Sat& b) { return Sa
 __device__ __forceinline__ Sat operator-(const Sat& a, const Sat& b) { return Sat{a.sn - b.sn, a.so - b.so, a.nv - b.nv}; }
 
 struct FssArgs {
-  const float* fc;
-  const float* truth;
-  const float* clim;   // nullptr: no anomaly event
-  const float* lat_w;  // [H]
-  const int* tr_slot;  // [L]
-  const int* cl_slot;  // [L]
-  const float* mean;   // [C] or nullptr (forecast already in physical units)
-  const float* sd;     // [C]
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs, cl_ss, cl_cs;
-  int M, E, S, H, W;
+  RolloutView v;     // clim nullptr: no anomaly event
+  int E, S;
   double* rec;       // [L][E][nrec][S][6]
   int* rec_inv;      // [L][E][nrec]
   unsigned* packed;  // [L][E][H W]
@@ -84,19 +75,17 @@ __device__ __forceinline__ long long plane_of(const FssArgs& a) { return static_
 template <int NMAX, bool INV, int DIR>
 __device__ __forceinline__ void count_body(const FssArgs& a) {
   const int e = blockIdx.y, l = blockIdx.z;
-  const int HW = a.H * a.W;
+  const int HW = a.v.H * a.v.W;
   const int p = blockIdx.x * TPB + threadIdx.x;
   const bool in = p < HW;
   const int pp = in ? p : 0;
   const int c = a.d.channel[e];
   const float thr = a.d.thr[e];
   const bool anom = a.d.anomaly[e] != 0;
-  const float* f = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs + pp;
-  const float t = a.truth[static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs + pp];
-  const float cl = anom ? a.clim[static_cast<long long>(a.cl_slot[l]) * a.cl_ss + static_cast<long long>(c) * a.cl_cs + pp] : 0.f;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
-  const EventPoint pt = classify_event_point<NMAX, INV, DIR>(f, a.fc_ms, a.M, t, cl, anom, thr, nrm);
+  const float t = view_truth(a.v, c, l)[pp];
+  const float cl = anom ? view_clim(a.v, c, l)[pp] : 0.f;
+  const EventPoint pt =
+      classify_event_point<NMAX, INV, DIR>(view_forecast(a.v, c, l) + pp, a.v.fc_ms, a.v.M, t, cl, anom, thr, view_norm<INV>(a.v, c));
   if (!in) return;
   const unsigned word = pt.valid ? static_cast<unsigned>(pt.n) | static_cast<unsigned>(pt.o) << O_BIT | 1u << V_BIT : 0u;
   a.packed[plane_of(a) * HW + p] = word;
@@ -112,9 +101,9 @@ __global__ __launch_bounds__(TPB) void fss_count_kernel(FssArgs a) {
 // Grid (H, E, L), one wave: row blockIdx.x of the plane, 64 columns per step.
 __global__ __launch_bounds__(64) void fss_rows_kernel(FssArgs a) {
   const int i = blockIdx.x, lane = threadIdx.x;
-  const int W = a.W, W1 = a.W + 1;
-  const unsigned* src = a.packed + plane_of(a) * a.H * W + static_cast<long long>(i) * W;
-  Sat* tab = a.sat + plane_of(a) * (a.H + 1) * W1;
+  const int W = a.v.W, W1 = a.v.W + 1;
+  const unsigned* src = a.packed + plane_of(a) * a.v.H * W + static_cast<long long>(i) * W;
+  Sat* tab = a.sat + plane_of(a) * (a.v.H + 1) * W1;
   if (i == 0)
     for (int j = lane; j < W1; j += 64) tab[j] = Sat{0u, 0u, 0u};
   Sat* dst = tab + static_cast<long long>(i + 1) * W1;
@@ -138,20 +127,20 @@ __global__ __launch_bounds__(64) void fss_rows_kernel(FssArgs a) {
 // Grid (ceil(W / 64), E, L), one wave: columns 1 .. W of the table, the running sum down rows 1 .. H (row 0 and column 0 stay zero).
 __global__ __launch_bounds__(64) void fss_cols_kernel(FssArgs a) {
   const int j = 1 + blockIdx.x * 64 + threadIdx.x;
-  if (j > a.W) return;
-  const int W1 = a.W + 1;
-  Sat* col = a.sat + plane_of(a) * (a.H + 1) * W1 + j;
+  if (j > a.v.W) return;
+  const int W1 = a.v.W + 1;
+  Sat* col = a.sat + plane_of(a) * (a.v.H + 1) * W1 + j;
   Sat acc{0u, 0u, 0u};
   constexpr int NB = 8;  // rows loaded before any is stored: the loads of a batch are in flight together (a store may alias a later load
                          // for all the compiler knows, so a plain loop waits for every load in turn)
-  for (int i0 = 1; i0 <= a.H; i0 += NB) {
+  for (int i0 = 1; i0 <= a.v.H; i0 += NB) {
     Sat v[NB];
 #pragma unroll
-    for (int k = 0; k < NB; ++k) v[k] = i0 + k <= a.H ? col[static_cast<long long>(i0 + k) * W1] : Sat{0u, 0u, 0u};
+    for (int k = 0; k < NB; ++k) v[k] = i0 + k <= a.v.H ? col[static_cast<long long>(i0 + k) * W1] : Sat{0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
       acc = acc + v[k];
-      if (i0 + k <= a.H) col[static_cast<long long>(i0 + k) * W1] = acc;
+      if (i0 + k <= a.v.H) col[static_cast<long long>(i0 + k) * W1] = acc;
     }
   }
 }
@@ -161,15 +150,15 @@ __global__ __launch_bounds__(TPB) void fss_window_kernel(FssArgs a) {
   __shared__ double red[LDC_FSS_SCALES_MAX][4][NT];
   __shared__ int red_i[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int H = a.H, W = a.W, W1 = a.W + 1, HW = a.H * a.W;
+  const int H = a.v.H, W = a.v.W, W1 = a.v.W + 1, HW = a.v.H * a.v.W;
   const int p = blockIdx.x * TPB + tid;
   const bool in = p < HW;
   const int pp = in ? p : 0;
   const int i = pp / W, j = pp - i * W;
   const long long plane = plane_of(a);
   const bool contrib = in && ((a.packed[plane * HW + pp] >> V_BIT) & 1u) != 0u;
-  const double w = contrib ? static_cast<double>(a.lat_w[i]) : 0.0;
-  const double dM = static_cast<double>(a.M);
+  const double w = contrib ? static_cast<double>(a.v.lat_w[i]) : 0.0;
+  const double dM = static_cast<double>(a.v.M);
   const Sat* tab = a.sat + plane * (H + 1) * W1;
   const double s_w = wave_sum(w);
   for (int s = 0; s < a.S; ++s) {
@@ -237,12 +226,9 @@ __global__ __launch_bounds__(128) void fss_finish_kernel(const double* __restric
 
 template <bool INV>
 void launch_count(const FssArgs& a, dim3 grid, hipStream_t s) {
-  const int M = a.M;
-  if (M <= 8) hipLaunchKernelGGL((fss_count_kernel<8, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 16) hipLaunchKernelGGL((fss_count_kernel<16, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 32) hipLaunchKernelGGL((fss_count_kernel<32, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 64) hipLaunchKernelGGL((fss_count_kernel<64, INV>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((fss_count_kernel<0, INV>), grid, dim3(TPB), 0, s, a);
+  ldc_dispatch_member_arm(a.v.M, [&](auto nmax) {
+    hipLaunchKernelGGL((fss_count_kernel<decltype(nmax)::value, INV>), grid, dim3(TPB), 0, s, a);
+  });
 }
 
 bool sizes_served(int M, int E, int S, int L, int H, int W) {
@@ -264,17 +250,16 @@ extern "C" int ldc_rollout_fss(const float* forecast, long long member_stride, l
                                long long clim_channel_stride, const int* clim_slot, const float* lat_weight, int M, int C, int L, int H, int W,
                                const ldc_events_desc* desc, const int* radii, int S, double* fss_sums, int* n_invalid, int L_total, int l_off,
                                void* workspace, long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(lat_weight);
+  FssArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, clim, clim_slot_stride, clim_channel_stride, clim_slot, lat_weight, M, C, L, H, W,
+                       L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(desc);
   LDC_CHECK_PTR(radii);
   LDC_CHECK_PTR(fss_sums);
   LDC_CHECK_PTR(n_invalid);
   LDC_CHECK_PTR(workspace);
-  if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   const int E = desc->n_events;
   if (E < 1 || E > LDC_EVENTS_MAX) return LDC_ERR_ARG;
   for (int e = 0; e < E; ++e) {
@@ -291,20 +276,7 @@ extern "C" int ldc_rollout_fss(const float* forecast, long long member_stride, l
   if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0 || (reinterpret_cast<uintptr_t>(fss_sums) & 7u) != 0) return LDC_ERR_ALIGN;  // fp64
   const Layout lay = layout_of(E, S, L, H, W);
   if (workspace_bytes < lay.total) return LDC_ERR_ARG;
-  FssArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.clim = clim;
-  a.lat_w = lat_weight;
-  a.tr_slot = truth_slot;
-  a.cl_slot = clim_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.cl_ss = clim_slot_stride; a.cl_cs = clim_channel_stride;
-  a.M = M; a.E = E; a.S = S; a.H = H; a.W = W;
+  a.E = E; a.S = S;
   char* ws = static_cast<char*>(workspace);
   a.rec = reinterpret_cast<double*>(ws + lay.rec);
   a.rec_inv = reinterpret_cast<int*>(ws + lay.rec_inv);

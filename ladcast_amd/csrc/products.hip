@@ -29,17 +29,13 @@ constexpr int MAX_Q = LDC_PRODUCTS_MAX_QUANTILES;
 constexpr int MAX_P = LDC_PRODUCTS_MAX_THRESHOLDS;
 
 struct ProdArgs {
-  const float* fc;
-  const float* mean;  // [C] or nullptr (forecast already in physical units)
-  const float* sd;    // [C]
-  const int* chan;    // [Cs] or nullptr (all channels, in order)
-  const float* thr;   // [P][Cs]
-  float* stats;       // [4][Cs][L_total][HW] or nullptr
-  float* quant;       // [Q][Cs][L_total][HW] or nullptr
-  float* exceed;      // [P][Cs][L_total][HW] or nullptr
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs;
-  int M, Cs, HW, L_total, l_off;
+  RolloutView v;     // the forecast only: no truth, no climatology
+  const int* chan;   // [Cs] or nullptr (all channels, in order)
+  const float* thr;  // [P][Cs]
+  float* stats;      // [4][Cs][L_total][HW] or nullptr
+  float* quant;      // [Q][Cs][L_total][HW] or nullptr
+  float* exceed;     // [P][Cs][L_total][HW] or nullptr
+  int Cs, HW, L_total, l_off;
   int Q, P;  // 0 when the output is not asked for
   ldc_products_desc d;
 };
@@ -77,10 +73,9 @@ __global__ __launch_bounds__(TPB) void products_kernel(ProdArgs a) {
   if (p >= a.HW) return;  // no barrier below
   const int cs = blockIdx.y, l = blockIdx.z;
   const int c = a.chan != nullptr ? a.chan[cs] : cs;
-  const int M = a.M, P = a.P;
-  const float* f = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs + p;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
+  const int M = a.v.M, P = a.P;
+  const float* f = view_forecast(a.v, c, l) + p;
+  const InvNorm nrm = view_norm<INV>(a.v, c);
   float thr[MAX_P];
   unsigned gt_mask = 0u;
 #pragma unroll
@@ -101,8 +96,7 @@ __global__ __launch_bounds__(TPB) void products_kernel(ProdArgs a) {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       if (i < NUSE && i < M) {
-        float v = f[static_cast<long long>(i) * a.fc_ms];
-        if constexpr (INV) v = inv_norm(v, nrm);
+        const float v = load_member<INV>(f, i, a.v.fc_ms, nrm);
         x[i] = v;
         pass1_add(s, v, thr, gt_mask, P);
       } else {
@@ -136,17 +130,11 @@ __global__ __launch_bounds__(TPB) void products_kernel(ProdArgs a) {
       }
     }
   } else {
-    for (int i = 0; i < M; ++i) {
-      float v = f[static_cast<long long>(i) * a.fc_ms];
-      if constexpr (INV) v = inv_norm(v, nrm);
-      pass1_add(s, v, thr, gt_mask, P);
-    }
+    for (int i = 0; i < M; ++i) pass1_add(s, load_member<INV>(f, i, a.v.fc_ms, nrm), thr, gt_mask, P);
     mean = s.sum / Mf;
     if (a.stats != nullptr) {
       for (int i = 0; i < M; ++i) {
-        float v = f[static_cast<long long>(i) * a.fc_ms];
-        if constexpr (INV) v = inv_norm(v, nrm);
-        const float e = v - mean;
+        const float e = load_member<INV>(f, i, a.v.fc_ms, nrm) - mean;
         ss += e * e;
       }
     }
@@ -170,7 +158,7 @@ template <bool INV>
 void launch_products(const ProdArgs& a, dim3 grid, hipStream_t s) {
   if (a.Q == 0) hipLaunchKernelGGL((products_kernel<0, 0, INV>), grid, dim3(TPB), 0, s, a);
   else
-    ldc_dispatch_sort_arm(a.M, [&](auto np, auto nuse) {
+    ldc_dispatch_sort_arm(a.v.M, [&](auto np, auto nuse) {
       hipLaunchKernelGGL((products_kernel<decltype(np)::value, decltype(nuse)::value, INV>), grid, dim3(TPB), 0, s, a);
     });
 }
@@ -183,9 +171,11 @@ extern "C" int ldc_rollout_products(const float* forecast, long long member_stri
                                     const float* mean, const float* std_, float target_std, const int* channels, int M, int C, int Cs, int L,
                                     int H, int W, const ldc_products_desc* desc, const float* thr, float* stats, float* quant, float* exceed,
                                     int L_total, int l_off, void* stream) {
-  LDC_CHECK_PTR(forecast);
+  ProdArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, nullptr, 0, 0, nullptr, nullptr, 0,
+                       0, nullptr, nullptr, M, C, L, H, W, L_total, l_off, /*with_truth=*/false) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(desc);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (Cs <= 0 || (channels == nullptr && Cs != C)) return LDC_ERR_ARG;
   if (desc->n_quant < 0 || desc->n_quant > MAX_Q || desc->n_thr < 0 || desc->n_thr > MAX_P) return LDC_ERR_ARG;
   const int Q = quant != nullptr ? desc->n_quant : 0;
@@ -200,18 +190,12 @@ extern "C" int ldc_rollout_products(const float* forecast, long long member_stri
     if (desc->thr_dir[k] != 1 && desc->thr_dir[k] != -1) return LDC_ERR_ARG;
   if (M > MAX_M || Cs > 65535 || L > 65535 || static_cast<long long>(H) * W > (1ll << 24)) return LDC_ERR_UNSUPPORTED;
   if (Q > 0 && M > MAX_SORT_M) return LDC_ERR_UNSUPPORTED;
-  ProdArgs a{};
-  a.fc = forecast;
-  a.mean = mean;
-  a.sd = std_;
   a.chan = channels;
   a.thr = thr;
   a.stats = stats;
   a.quant = quant;
   a.exceed = exceed;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.M = M; a.Cs = Cs; a.HW = H * W; a.L_total = L_total; a.l_off = l_off;
+  a.Cs = Cs; a.HW = H * W; a.L_total = L_total; a.l_off = l_off;
   a.Q = Q; a.P = P;
   a.d = *desc;
   dim3 grid(ldc_cdiv(a.HW, TPB), Cs, L);

@@ -43,20 +43,10 @@ constexpr int REC_BYTES = MAX_R * (NS * 8 + 4 * 4);
 constexpr int REC_CNT_OFF = MAX_R * NS * 8;  // the counts follow the sums: [32][4] int32
 
 struct RegArgs {
-  const float* fc;
-  const float* truth;
-  const float* clim;    // nullptr: no ACC terms
-  const float* lat_w;   // [H]
+  RolloutView v;        // clim nullptr: no ACC terms
   const unsigned* reg;  // [H * W]
-  const int* tr_slot;   // [L]
-  const int* cl_slot;   // [L]
-  const float* mean;    // [C] or nullptr (forecast already in physical units)
-  const float* sd;      // [C]
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs, cl_ss, cl_cs;
-  int M, C, H, W, R;
   unsigned char* part;  // [L][C][nrec][REC_BYTES]
-  int ntile, nrec;
+  int R, ntile, nrec;
 };
 
 template <int NP, int NUSE, bool INV>
@@ -64,16 +54,15 @@ __global__ __launch_bounds__(TPB) void regional_kernel(RegArgs a) {
   __shared__ __attribute__((aligned(16))) double s_val[TPB * NS];
   __shared__ __attribute__((aligned(16))) unsigned s_m[3][TPB];  // valid, ACC-valid, invalid
   const int c = blockIdx.y, l = blockIdx.z;
-  const int M = a.M;
-  const int HW = a.H * a.W;
+  const int M = a.v.M;
+  const int HW = a.v.H * a.v.W;
   const int tid = threadIdx.x;
   const int r = tid & 31, s = tid >> 5;
   const unsigned rmask = a.R >= 32 ? 0xffffffffu : ((1u << a.R) - 1u);
-  const float* fbase = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs;
-  const float* tbase = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs;
-  const float* cbase = a.clim ? a.clim + static_cast<long long>(a.cl_slot[l]) * a.cl_ss + static_cast<long long>(c) * a.cl_cs : nullptr;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
+  const float* fbase = view_forecast(a.v, c, l);
+  const float* tbase = view_truth(a.v, c, l);
+  const float* cbase = view_clim(a.v, c, l);
+  const InvNorm nrm = view_norm<INV>(a.v, c);
   const float Mf = static_cast<float>(M);
   double acc0 = 0.0, acc1 = 0.0;
   int n_val = 0, n_inv = 0, n_acc = 0;
@@ -93,8 +82,7 @@ __global__ __launch_bounds__(TPB) void regional_kernel(RegArgs a) {
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
         if (i < NUSE && i < M) {
-          float v = f[static_cast<long long>(i) * a.fc_ms];
-          if constexpr (INV) v = inv_norm(v, nrm);
+          const float v = load_member<INV>(f, i, a.v.fc_ms, nrm);
           x[i] = v;
           sum += v;
           nan_m = nan_m || (v != v);
@@ -103,7 +91,7 @@ __global__ __launch_bounds__(TPB) void regional_kernel(RegArgs a) {
         }
       }
       const float t = tbase[p];
-      const float w = a.lat_w[p / a.W];
+      const float w = a.v.lat_w[p / a.v.W];
       float skill = 0.f;
 #pragma unroll
       for (int i = 0; i < NUSE; ++i)
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(TPB) void regional_kernel(RegArgs a) {
     }
   }
   // the record: every entry of every region is written, zeros where the workgroup met no point (or no climatology)
-  unsigned char* rec = a.part + ((static_cast<long long>(l) * a.C + c) * a.nrec + blockIdx.x) * REC_BYTES;
+  unsigned char* rec = a.part + ((static_cast<long long>(l) * a.v.C + c) * a.nrec + blockIdx.x) * REC_BYTES;
   if (s < 5) {
     double* d = reinterpret_cast<double*>(rec) + r * NS + 2 * s;
     d[0] = acc0;
@@ -229,7 +217,7 @@ __global__ __launch_bounds__(TPB) void regional_finish_kernel(const unsigned cha
 
 template <bool INV>
 void launch_regional(const RegArgs& a, dim3 grid, hipStream_t s) {
-  ldc_dispatch_sort_arm(a.M, [&](auto np, auto nuse) {
+  ldc_dispatch_sort_arm(a.v.M, [&](auto np, auto nuse) {
     hipLaunchKernelGGL((regional_kernel<decltype(np)::value, decltype(nuse)::value, INV>), grid, dim3(TPB), 0, s, a);
   });
 }
@@ -250,35 +238,21 @@ extern "C" int ldc_rollout_regional(const float* forecast, long long member_stri
                                     long long clim_channel_stride, const int* clim_slot, const float* lat_weight,
                                     const unsigned* region_mask, int R, int M, int C, int L, int H, int W, double* sums, int* counts,
                                     int L_total, int l_off, void* workspace, long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(lat_weight);
+  RegArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, clim, clim_slot_stride, clim_channel_stride, clim_slot, lat_weight, M, C, L, H, W,
+                       L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(region_mask);
   LDC_CHECK_PTR(sums);
   LDC_CHECK_PTR(counts);
   LDC_CHECK_PTR(workspace);
-  if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (R <= 0) return LDC_ERR_ARG;
   if (M > 64 || R > MAX_R || C > 65535 || L > 65535 || static_cast<long long>(H) * W > (1ll << 24)) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_regional_workspace_bytes(M, R, C, L, H, W)) return LDC_ERR_ARG;
   if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0 || (reinterpret_cast<uintptr_t>(sums) & 7u) != 0) return LDC_ERR_ALIGN;  // fp64
-  RegArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.clim = clim;
-  a.lat_w = lat_weight;
   a.reg = region_mask;
-  a.tr_slot = truth_slot;
-  a.cl_slot = clim_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.cl_ss = clim_slot_stride; a.cl_cs = clim_channel_stride;
-  a.M = M; a.C = C; a.H = H; a.W = W; a.R = R;
+  a.R = R;
   a.part = static_cast<unsigned char*>(workspace);
   a.ntile = ldc_cdiv(static_cast<long long>(H) * W, TPB);
   a.nrec = ldc_cdiv(a.ntile, TPW);

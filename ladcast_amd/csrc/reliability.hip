@@ -34,15 +34,7 @@ constexpr int tiles_per_wg(int M) { return M <= 64 ? 1 : (M + 63) / 64; }
 constexpr int rec_words(int M) { return HEAD + 2 * (M + 1); }
 
 struct RelArgs {
-  const float* fc;
-  const float* truth;
-  const float* lat_w;  // [H]
-  const int* tr_slot;  // [L]
-  const float* mean;   // [C] or nullptr (forecast already in physical units)
-  const float* sd;     // [C]
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs;
-  int M, C, H, W;
+  RolloutView v;   // no climatology
   unsigned* part;  // [L][C][nrec][rec_words(M)]
   int ntile, tpw, nrec;
 };
@@ -57,13 +49,12 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
   __shared__ float red_f[4][2];
   __shared__ int red_i[4][4];
   const int c = blockIdx.y, l = blockIdx.z;
-  const int M = a.M;
-  const int HW = a.H * a.W;
+  const int M = a.v.M;
+  const int HW = a.v.H * a.v.W;
   const int tid = threadIdx.x;
-  const float* fbase = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs;
-  const float* tbase = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
+  const float* fbase = view_forecast(a.v, c, l);
+  const float* tbase = view_truth(a.v, c, l);
+  const InvNorm nrm = view_norm<INV>(a.v, c);
   const float Mf = static_cast<float>(M);
   float acc_se = 0.f, acc_var = 0.f;
   int n_se = 0, n_var = 0, n_in = 0, n_inv = 0;
@@ -82,7 +73,7 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
     const int pp = in ? p : 0;
     const float* f = fbase + pp;
     const float t = tbase[pp];
-    const float w = a.lat_w[pp / a.W];
+    const float w = a.v.lat_w[pp / a.v.W];
     float sum = 0.f, ss = 0.f;
     int lt = 0, eq = 0;
     bool nan_m = false;
@@ -92,8 +83,7 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
         if (i < M) {
-          float v = f[static_cast<long long>(i) * a.fc_ms];
-          if constexpr (INV) v = inv_norm(v, nrm);
+          const float v = load_member<INV>(f, i, a.v.fc_ms, nrm);
           x[i] = v;
           sum += v;
           nan_m = nan_m || (v != v);
@@ -112,8 +102,7 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
         }
     } else {
       for (int i = 0; i < M; ++i) {
-        float v = f[static_cast<long long>(i) * a.fc_ms];
-        if constexpr (INV) v = inv_norm(v, nrm);
+        const float v = load_member<INV>(f, i, a.v.fc_ms, nrm);
         sum += v;
         nan_m = nan_m || (v != v);
         lt += v < t ? 1 : 0;
@@ -121,9 +110,7 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
       }
       mean = sum / Mf;
       for (int i = 0; i < M; ++i) {
-        float v = f[static_cast<long long>(i) * a.fc_ms];
-        if constexpr (INV) v = inv_norm(v, nrm);
-        const float e = v - mean;
+        const float e = load_member<INV>(f, i, a.v.fc_ms, nrm) - mean;
         ss += e * e;
       }
     }
@@ -166,7 +153,7 @@ __global__ __launch_bounds__(TPB) void reliability_kernel(RelArgs a) {
       }
     }
   }
-  unsigned* rec = a.part + ((static_cast<long long>(l) * a.C + c) * a.nrec + blockIdx.x) * rec_words(M);
+  unsigned* rec = a.part + ((static_cast<long long>(l) * a.v.C + c) * a.nrec + blockIdx.x) * rec_words(M);
 #pragma unroll
   for (int k = 0; k < KB; ++k) {
     const int b = tid + k * TPB;
@@ -250,12 +237,9 @@ __global__ __launch_bounds__(TPB) void reliability_finish_kernel(const unsigned*
 
 template <bool INV>
 void launch_reliability(const RelArgs& a, dim3 grid, hipStream_t s) {
-  const int M = a.M;
-  if (M <= 8) hipLaunchKernelGGL((reliability_kernel<8, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 16) hipLaunchKernelGGL((reliability_kernel<16, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 32) hipLaunchKernelGGL((reliability_kernel<32, INV>), grid, dim3(TPB), 0, s, a);
-  else if (M <= 64) hipLaunchKernelGGL((reliability_kernel<64, INV>), grid, dim3(TPB), 0, s, a);
-  else hipLaunchKernelGGL((reliability_kernel<0, INV>), grid, dim3(TPB), 0, s, a);
+  ldc_dispatch_member_arm(a.v.M, [&](auto nmax) {
+    hipLaunchKernelGGL((reliability_kernel<decltype(nmax)::value, INV>), grid, dim3(TPB), 0, s, a);
+  });
 }
 
 }  // namespace
@@ -273,29 +257,17 @@ extern "C" int ldc_rollout_reliability(const float* forecast, long long member_s
                                        const float* lat_weight, int M, int C, int L, int H, int W, int nan_channel, float* out,
                                        int* hist_count, float* hist_weight, int* n_invalid, int L_total, int l_off, void* workspace,
                                        long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(lat_weight);
+  RelArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, nullptr, 0, 0, nullptr, lat_weight, M, C, L, H, W, L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(out);
   LDC_CHECK_PTR(hist_count);
   LDC_CHECK_PTR(hist_weight);
   LDC_CHECK_PTR(n_invalid);
   LDC_CHECK_PTR(workspace);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (M > MAX_M || C > 65535 || L > 65535 || static_cast<long long>(H) * W > (1ll << 24)) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_reliability_workspace_bytes(M, C, L, H, W)) return LDC_ERR_ARG;
-  RelArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.lat_w = lat_weight;
-  a.tr_slot = truth_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.M = M; a.C = C; a.H = H; a.W = W;
   a.part = static_cast<unsigned*>(workspace);
   a.ntile = ldc_cdiv(static_cast<long long>(H) * W, TPB);
   a.tpw = tiles_per_wg(M);

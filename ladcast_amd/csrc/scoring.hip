@@ -61,8 +61,7 @@ __device__ __forceinline__ void score_point(const float* f, long long ms, int M,
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     if (i < NUSE && i < M) {
-      float v = f[static_cast<long long>(i) * ms];
-      if constexpr (INV) v = inv_norm(v, nrm);
+      const float v = load_member<INV>(f, i, ms, nrm);
       x[i] = v;
       sum += v;  // same left-to-right order as torch's mean over dim 0 for small M is not guaranteed; tolerance in tests
       nan_m = nan_m || (v != v);
@@ -160,21 +159,10 @@ __global__ __launch_bounds__(TPB) void ensemble_scores_kernel(ScoreArgs a) {
                                a.part + (static_cast<long long>(c) * a.nblk + blockIdx.x) * (NQ + 7), InvNorm{});
 }
 
-// Every lead time of a decode batch in one launch: grid (nblk, C, L).  The forecast is addressed by member / lead / channel strides
-// (the (ens, C, T, H, W) array or the decoder's frame-major (L * ens, C, H, W) output), truth and climatology are tables of planes
-// with a slot per lead time; the optional inverse normalisation is applied to every forecast value as it is loaded.
+// Every lead time of a decode batch in one launch: grid (nblk, C, L).  The forecast, truth and climatology (nullptr = no ACC) are addressed
+// through the RolloutView; the optional inverse normalisation is applied to every forecast value as it is loaded.
 struct RolloutArgs {
-  const float* fc;
-  const float* truth;
-  const float* clim;   // nullptr = no ACC
-  const float* lat_w;  // [H]
-  const int* tr_slot;  // [L]
-  const int* cl_slot;  // [L]
-  const float* mean;   // [C] or nullptr (forecast already in physical units)
-  const float* sd;     // [C]
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs, cl_ss, cl_cs;
-  int M, C, H, W;
+  RolloutView v;
   float* part;  // [L][C][nblk][nrec(SINGLE)]
   int nblk;
 };
@@ -182,17 +170,15 @@ struct RolloutArgs {
 template <int NP, int NUSE, bool INV, bool SINGLE>
 __global__ __launch_bounds__(TPB) void rollout_scores_kernel(RolloutArgs a) {
   const int c = blockIdx.y, l = blockIdx.z;
-  const int HW = a.H * a.W;
+  const int HW = a.v.H * a.v.W;
   const int p = blockIdx.x * TPB + threadIdx.x;
   const bool in = p < HW;
   const int pp = in ? p : 0;
-  const float* f = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs + pp;
-  const float* tp = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs + pp;
-  const float* clp = a.clim ? a.clim + static_cast<long long>(a.cl_slot[l]) * a.cl_ss + static_cast<long long>(c) * a.cl_cs + pp : nullptr;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
-  score_point<NP, NUSE, INV, SINGLE>(f, a.fc_ms, a.M, tp, clp, a.lat_w + pp / a.W, in, nullptr, nullptr,
-                                     a.part + ((static_cast<long long>(l) * a.C + c) * a.nblk + blockIdx.x) * nrec(SINGLE), nrm);
+  const float* clp = view_clim(a.v, c, l);
+  score_point<NP, NUSE, INV, SINGLE>(view_forecast(a.v, c, l) + pp, a.v.fc_ms, a.v.M, view_truth(a.v, c, l) + pp, clp ? clp + pp : nullptr,
+                                     a.v.lat_w + pp / a.v.W, in, nullptr, nullptr,
+                                     a.part + ((static_cast<long long>(l) * a.v.C + c) * a.nblk + blockIdx.x) * nrec(SINGLE),
+                                     view_norm<INV>(a.v, c));
 }
 
 // The five scores of one (channel, lead time) from its nblk partial records.  One wave: lane j adds the partial records
@@ -317,7 +303,7 @@ extern "C" long long ldc_rollout_scores_workspace_bytes(int C, int L, int H, int
 namespace {
 template <bool INV, bool SINGLE = false>
 void launch_rollout(const RolloutArgs& a, dim3 grid, hipStream_t s) {
-  ldc_dispatch_sort_arm(a.M, [&](auto np, auto nuse) {
+  ldc_dispatch_sort_arm(a.v.M, [&](auto np, auto nuse) {
     hipLaunchKernelGGL((rollout_scores_kernel<decltype(np)::value, decltype(nuse)::value, INV, SINGLE>), grid, dim3(TPB), 0, s, a);
   });
 }
@@ -329,30 +315,15 @@ extern "C" int ldc_rollout_scores(const float* forecast, long long member_stride
                                   long long clim_slot_stride, long long clim_channel_stride, const int* clim_slot,
                                   const float* lat_weight, int M, int C, int L, int H, int W, int nan_channel, float* out, int L_total,
                                   int l_off, void* workspace, long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(lat_weight);
+  RolloutArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, clim, clim_slot_stride, clim_channel_stride, clim_slot, lat_weight, M, C, L, H, W,
+                       L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(out);
   LDC_CHECK_PTR(workspace);
-  if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (M > 64 || C > 65535 || L > 65535) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_scores_workspace_bytes(C, L, H, W)) return LDC_ERR_ARG;
-  RolloutArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.clim = clim;
-  a.lat_w = lat_weight;
-  a.tr_slot = truth_slot;
-  a.cl_slot = clim_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.cl_ss = clim_slot_stride; a.cl_cs = clim_channel_stride;
-  a.M = M; a.C = C; a.H = H; a.W = W;
   a.part = static_cast<float*>(workspace);
   a.nblk = static_cast<int>(ldc_cdiv(static_cast<long long>(H) * W, TPB));
   dim3 grid(a.nblk, C, L);
@@ -378,26 +349,14 @@ extern "C" int ldc_validation_scores(const float* forecast, long long member_str
                                      long long truth_slot_stride, long long truth_channel_stride, const int* truth_slot,
                                      const float* lat_weight, int M, int C, int L, int H, int W, float* out, int L_total, int l_off,
                                      void* workspace, long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(lat_weight);
+  RolloutArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, nullptr, 0, 0, nullptr, lat_weight, M, C, L, H, W, L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(out);
   LDC_CHECK_PTR(workspace);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (M > 64 || C > 65535 || L > 65535) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_validation_scores_workspace_bytes(C, L, H, W)) return LDC_ERR_ARG;
-  RolloutArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.lat_w = lat_weight;
-  a.tr_slot = truth_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.M = M; a.C = C; a.H = H; a.W = W;
   a.part = static_cast<float*>(workspace);
   a.nblk = static_cast<int>(ldc_cdiv(static_cast<long long>(H) * W, TPB));
   dim3 grid(a.nblk, C, L);

@@ -32,15 +32,7 @@ constexpr long long TABLE_BYTES = MAX_W * 2 * sizeof(float);  // front of the wo
 constexpr int rec_doubles(int K) { return 2 + 3 * K; }  // sum of weights; (n_invalid, n_valid) as two int32; [3][K] sums
 
 struct SpecArgs {
-  const float* fc;
-  const float* truth;
-  const float* row_w;  // [H]
-  const int* tr_slot;  // [L]
-  const float* mean;   // [C] or nullptr (forecast already in physical units)
-  const float* sd;     // [C]
-  float target_std;
-  long long fc_ms, fc_ls, fc_cs, tr_ss, tr_cs;
-  int M, C, H, W;
+  RolloutView v;        // no climatology; lat_w holds row_weight
   const float2* table;  // [W] (cos, sin)(2 pi i / W)
   double* rec;          // [L][C][nrec][rec_doubles(K)]
   int nrec;
@@ -64,12 +56,11 @@ __global__ __launch_bounds__(WAVE) void spectrum_kernel(SpecArgs a) {
   __shared__ float s_mean[WMAX];
   __shared__ __attribute__((aligned(16))) float s_eo[WMAX / 2 + 1][2][SB];
   const int c = blockIdx.y, l = blockIdx.z, t = threadIdx.x;
-  const int M = a.M, W = a.W, half = W >> 1, K = half + 1;
+  const int M = a.v.M, W = a.v.W, half = W >> 1, K = half + 1;
   const float Mf = static_cast<float>(M), Wf = static_cast<float>(W);
-  const float* fbase = a.fc + static_cast<long long>(l) * a.fc_ls + static_cast<long long>(c) * a.fc_cs;
-  const float* tbase = a.truth + static_cast<long long>(a.tr_slot[l]) * a.tr_ss + static_cast<long long>(c) * a.tr_cs;
-  InvNorm nrm{};
-  if constexpr (INV) nrm = make_inv_norm(a.target_std, a.sd, a.mean, c);
+  const float* fbase = view_forecast(a.v, c, l);
+  const float* tbase = view_truth(a.v, c, l);
+  const InvNorm nrm = view_norm<INV>(a.v, c);
   for (int i = t; i < W; i += WAVE) s_tw[i] = a.table[i];
   int kk[KB];  // the lane's bins; 0: none (the table's entry 0 is read, nothing is kept)
 #pragma unroll
@@ -83,9 +74,9 @@ __global__ __launch_bounds__(WAVE) void spectrum_kernel(SpecArgs a) {
   int n_invalid = 0, n_valid = 0;
   const int nblk = (M + 2 + SB - 1) / SB;
 
-  const int h1 = min((static_cast<int>(blockIdx.x) + 1) * RPW, a.H);
+  const int h1 = min((static_cast<int>(blockIdx.x) + 1) * RPW, a.v.H);
   for (int h = blockIdx.x * RPW; h < h1; ++h) {
-    const float w = a.row_w[h];
+    const float w = a.v.lat_w[h];
     if (!(w > 0.f)) continue;  // not read at all
     const float* frow = fbase + static_cast<long long>(h) * W;
     const float* trow = tbase + static_cast<long long>(h) * W;
@@ -95,13 +86,11 @@ __global__ __launch_bounds__(WAVE) void spectrum_kernel(SpecArgs a) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) sum[q] = 0.f;
     for (int i = 0; i < M; ++i) {
-      const float* f = frow + static_cast<long long>(i) * a.fc_ms;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         const int j = t + WAVE * q;
         if (j < W) {
-          float v = f[j];
-          if constexpr (INV) v = inv_norm(v, nrm);
+          const float v = load_member<INV>(frow + j, i, a.v.fc_ms, nrm);
           sum[q] += v;
           bad = bad || (v != v);
         }
@@ -128,11 +117,7 @@ __global__ __launch_bounds__(WAVE) void spectrum_kernel(SpecArgs a) {
     for (int blk = 0; blk < nblk; ++blk) {
       // sequence q: member q < M, the ensemble mean (M), the truth (M + 1), nothing beyond
       auto value = [&](int q, int j) -> float {
-        if (q < M) {
-          float v = frow[static_cast<long long>(q) * a.fc_ms + j];
-          if constexpr (INV) v = inv_norm(v, nrm);
-          return v;
-        }
+        if (q < M) return load_member<INV>(frow + j, q, a.v.fc_ms, nrm);
         if (q == M) return s_mean[j];
         if (q == M + 1) return trow[j];
         return 0.f;
@@ -221,7 +206,7 @@ __global__ __launch_bounds__(WAVE) void spectrum_kernel(SpecArgs a) {
       for (int b = 0; b < KB; ++b) tot[b][pl] += wd * acc[b][pl];
     }
   }
-  double* rec = a.rec + ((static_cast<long long>(l) * a.C + c) * a.nrec + blockIdx.x) * rec_doubles(K);
+  double* rec = a.rec + ((static_cast<long long>(l) * a.v.C + c) * a.nrec + blockIdx.x) * rec_doubles(K);
   if (t == 0) {
     rec[0] = wsum;
     reinterpret_cast<int*>(rec + 1)[0] = n_invalid;
@@ -273,7 +258,7 @@ __global__ __launch_bounds__(256) void spectrum_finish_kernel(const double* __re
 
 template <bool INV>
 void launch_spectrum(const SpecArgs& a, dim3 grid, hipStream_t s) {
-  const int W = a.W;
+  const int W = a.v.W;
   if (W <= 128) hipLaunchKernelGGL((spectrum_kernel<1, INV>), grid, dim3(WAVE), 0, s, a);
   else if (W <= 256) hipLaunchKernelGGL((spectrum_kernel<2, INV>), grid, dim3(WAVE), 0, s, a);
   else if (W <= 384) hipLaunchKernelGGL((spectrum_kernel<3, INV>), grid, dim3(WAVE), 0, s, a);
@@ -297,28 +282,16 @@ extern "C" int ldc_rollout_spectrum(const float* forecast, long long member_stri
                                     long long truth_channel_stride, const int* truth_slot, const float* row_weight, int M, int C, int L, int H,
                                     int W, float* out, int* n_invalid, int L_total, int l_off, void* workspace, long long workspace_bytes,
                                     void* stream) {
-  LDC_CHECK_PTR(forecast);
-  LDC_CHECK_PTR(truth);
-  LDC_CHECK_PTR(truth_slot);
-  LDC_CHECK_PTR(row_weight);
+  SpecArgs a{};
+  if (ldc_rollout_view(&a.v, forecast, member_stride, lead_stride, channel_stride, mean, std_, target_std, truth, truth_slot_stride,
+                       truth_channel_stride, truth_slot, nullptr, 0, 0, nullptr, row_weight, M, C, L, H, W, L_total, l_off) != LDC_OK)
+    return LDC_ERR_ARG;
   LDC_CHECK_PTR(out);
   LDC_CHECK_PTR(n_invalid);
   LDC_CHECK_PTR(workspace);
-  if (ldc_check_forecast_args(M, C, L, H, W, L_total, l_off, mean, std_) != LDC_OK) return LDC_ERR_ARG;
   if (!served(M, C, L, H, W)) return LDC_ERR_UNSUPPORTED;
   if (workspace_bytes < ldc_rollout_spectrum_workspace_bytes(M, C, L, H, W)) return LDC_ERR_ARG;
   LDC_CHECK_ALIGN16(workspace);
-  SpecArgs a{};
-  a.fc = forecast;
-  a.truth = truth;
-  a.row_w = row_weight;
-  a.tr_slot = truth_slot;
-  a.mean = mean;
-  a.sd = std_;
-  a.target_std = target_std;
-  a.fc_ms = member_stride; a.fc_ls = lead_stride; a.fc_cs = channel_stride;
-  a.tr_ss = truth_slot_stride; a.tr_cs = truth_channel_stride;
-  a.M = M; a.C = C; a.H = H; a.W = W;
   float2* table = static_cast<float2*>(workspace);
   a.table = table;
   a.rec = reinterpret_cast<double*>(static_cast<char*>(workspace) + TABLE_BYTES);
