@@ -961,6 +961,45 @@ long long ldc_field_moments_workspace_bytes(int B, int C, int H, int W);
 int ldc_field_moments(const float* x, long long batch_stride, long long channel_stride, long long row_stride, int B, int C, int H,
                       int W, double* state, int accumulate, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Day-of-year climatology from raw frames (climatology.hip; the reference reads a ready-made climatology and has no code that makes
+ * one).  Additive: ABI 5.  The table evaluate_ens_gpu reads as --climatology_path: (day of year, hour, channel, row, column).
+ *
+ * Accumulate.  x[b*batch_stride + c*channel_stride + h*row_stride + w], b < B, c < C, h < H, w < W (fp32; strided as in
+ * the field moments above: a row crop is the caller's row offset, a channel block a channel offset and a smaller C, no copy).
+ * slots: device int[B]; frame b belongs to slot slots[b]; an entry outside [0, n_slots) skips the frame (nothing of it is read or
+ * written).  sum: dense double[n_slots][C][H][W], count: dense int[n_slots][C][H][W], both zero-filled ONCE by the caller before the
+ * first call and then only passed on from call to call.  For every non-NaN value (only NaN is skipped; +-inf is a value):
+ *   sum[slot][c][h][w] += x (fp64),  count[slot][c][h][w] += 1
+ * in frame order b = 0 .. B - 1, one thread per point: two frames of a batch that share a slot add in frame order, and the state
+ * after a dataset holds the same bits however its frames were cut into batches.  Elements no valid value falls on are not written.
+ * 16-byte loads of x and count and 16-byte read-modify-writes of sum when W % 4 == 0 and x, sum, count and the three strides keep
+ * 16-byte alignment; a scalar path otherwise.
+ * LDC_ERR_ARG: a null pointer, a non-positive size (B, C, H, W, n_slots) or row_stride < W; LDC_ERR_ALIGN: x, slots or count not
+ * 4-byte or sum not 8-byte aligned; LDC_ERR_UNSUPPORTED: C * H above 2^31 - 1, more than 2^31 - 1 workgroups of 256 threads (one
+ * thread per 4 points, or per point on the scalar path) or a state of 2^62 elements or more.
+ *
+ * Smooth.  sum and count viewed as [n_days][n_hours][points], points = C * plane (plane = H * W of the accumulate call, n_slots =
+ * n_days * n_hours, slot = day * n_hours + hour); weights: device double[window], window odd, the weight of day offset
+ * k - (window - 1) / 2 at index k; out: float[n_days][n_hours][points], every element written:
+ *   out[d][h][p] = (sum_k weights[k] sum[(d + k - r) mod n_days][h][p]) / (sum_k weights[k] count[(d + k - r) mod n_days][h][p]),
+ *   r = (window - 1) / 2: the weighted mean of all samples in the window, each weighted by its day offset; the day axis is circular,
+ *   hours are never mixed.  Both sums run over k = 0 .. window - 1 in order as fp64 fused multiply-adds, the quotient is rounded to
+ *   fp64 and then once to fp32.  NaN where the denominator is 0.  window = 1, weights = {1}: the plain mean of each slot.
+ * n_empty (optional, NULL = not counted): long long[C], zero-filled by the caller; the kernel ADDS per channel the number of
+ * (day, hour, point) outputs whose denominator is 0 (integer atomics, at most one per workgroup and channel).
+ * sum, count and weights are only read.  A workgroup stages the whole day column of 32 consecutive points of one hour in LDS
+ * (392 bytes per day), so every state element is read from memory once per launch; n_days <= 417 (160 KiB of LDS).
+ * LDC_ERR_ARG: a null pointer (n_empty excepted), a non-positive size (n_days, n_hours, C, plane), window < 1, window even or
+ * window > n_days; LDC_ERR_ALIGN: sum, weights or n_empty not 8-byte, count or out not 4-byte aligned; LDC_ERR_UNSUPPORTED:
+ * n_days > 417, more than 2^31 - 1 workgroups (n_hours * ceil(points / 32)) or a table of 2^62 elements or more.
+ *
+ * Both: nothing is launched or written on an error.  No float atomics: the same call sequence gives the same bits. */
+int ldc_climatology_accumulate(const float* x, long long batch_stride, long long channel_stride, long long row_stride, int B, int C,
+                               int H, int W, const int* slots, int n_slots, double* sum, int* count, void* stream);
+int ldc_climatology_smooth(const double* sum, const int* count, const double* weights, int window, int n_days, int n_hours, int C,
+                           long long plane, float* out, long long* n_empty, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

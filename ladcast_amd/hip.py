@@ -197,6 +197,8 @@ def _load():
         "ldc_recon_scores": (I, [P, P, P, L, P, P, P, P, I, I, I, I, I, I, P, P, P, P, L, P]),
         "ldc_field_moments_workspace_bytes": (L, [I, I, I, I]),
         "ldc_field_moments": (I, [P, L, L, L, I, I, I, I, P, I, P, L, P]),
+        "ldc_climatology_accumulate": (I, [P, L, L, L, I, I, I, I, P, I, P, P, P]),
+        "ldc_climatology_smooth": (I, [P, P, P, I, I, I, I, L, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -650,6 +652,22 @@ def field_moments(x, state, *, B, C, H, W, batch_stride, channel_stride, row_str
     ws = _workspace("field_moments", x.device, max(nbytes, 16), grow=True)
     _check(lib.ldc_field_moments(_p(x), batch_stride, channel_stride, row_stride, B, C, H, W, _p(state), 1 if accumulate else 0, _p(ws),
                                  ws.numel() * 4, _stream()), "ldc_field_moments")
+
+
+def climatology_accumulate(x, slots, sum, count, *, B, C, H, W, n_slots, batch_stride, channel_stride, row_stride):
+    """sum (fp64) / count (int32) [n_slots][C][H][W] += the non-NaN values of frame b of the strided fp32 batch x at slot slots[b]
+    (device int32 [B]; outside [0, n_slots): skipped), in frame order (ladcast_hip.h: ldc_climatology_accumulate)"""
+    _dev(x, slots, sum, count)
+    _check(lib.ldc_climatology_accumulate(_p(x), batch_stride, channel_stride, row_stride, B, C, H, W, _p(slots), n_slots, _p(sum), _p(count),
+                                          _stream()), "ldc_climatology_accumulate")
+
+
+def climatology_smooth(sum, count, weights, out, n_empty=None, *, n_days, n_hours, C, plane):
+    """out (fp32) [n_days][n_hours][C * plane] = the weighted mean over the circular day window (weights: device fp64 [window]) of the
+    accumulated state; n_empty (int64 [C], zeroed by the caller) += the outputs without a sample (ladcast_hip.h: ldc_climatology_smooth)"""
+    _dev(sum, count, weights, out, n_empty)
+    _check(lib.ldc_climatology_smooth(_p(sum), _p(count), _p(weights), int(weights.numel()), n_days, n_hours, C, plane, _p(out), _p(n_empty),
+                                      _stream()), "ldc_climatology_smooth")
 
 
 def compact_rope_table(cos, sin):
