@@ -1000,6 +1000,42 @@ int ldc_climatology_accumulate(const float* x, long long batch_stride, long long
 int ldc_climatology_smooth(const double* sum, const int* count, const double* weights, int window, int n_days, int n_hours, int C,
                            long long plane, float* out, long long* n_empty, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Paired block-bootstrap comparison of two scored runs (bootstrap.hip; no counterpart in the reference).  Additive: ABI 5.
+ *
+ * a, b: the scores of runs A and B, fp32, N paired initial times by K series, element (i, k) at [i*ld + k], ld >= K (a slice of the
+ * series of a wider array is passed without a copy).  draws: device int[R][D], R replicates of D resampled initial times, every
+ * value in [0, N) (the caller's contract; a value outside is dropped, never written through).  The resampling scheme is the host's.
+ * kind: 0 = mean, theta = S / m;  1 = root mean, theta = sqrt(S / m) (RMSE from per-time MSE).  tail_ppm: the tail probability of
+ * the interval on each side in parts per million (25000: a 95 % interval), 0 <= tail_ppm < 500000.
+ *
+ * Per series k.  Pair i is valid when a[i,k] and b[i,k] are both finite; invalid pairs are skipped everywhere.
+ *   n_valid = the valid pairs;  a_hat, b_hat = theta over them;  diff_hat = b_hat - a_hat;  ratio_hat = b_hat / a_hat.
+ *   Replicate r: SA_r, SB_r = the fp64 sums over its valid draws, m_r their number; m_r == 0: the replicate is unused.  Otherwise
+ *   a*_r, b*_r = theta of the sums, d*_r = b*_r - a*_r, q*_r = b*_r / a*_r.
+ *   n_used = the replicates with m_r > 0 and finite d*_r;  n_le0 / n_ge0 = those of them with d* <= 0 / d* >= 0.
+ *   Interval of diff: the n_used finite d* sorted ascending, lo = (tail_ppm * n_used) / 1000000 (64-bit integer division),
+ *   hi = n_used - 1 - lo, diff_lo = sorted[lo], diff_hi = sorted[hi]; no interpolation.  Interval of ratio: the same over the finite
+ *   q*, with their own count.  (The order is that of the values, -0 before +0.)
+ *   stats[k] = { a_hat, b_hat, diff_hat, ratio_hat, diff_lo, diff_hi, ratio_lo, ratio_hi } (double[K][8]);
+ *   counts[k] = { n_valid, n_used, n_le0, n_ge0 } (int[K][4]).  n_valid == 0: the four estimates are NaN; no finite d* (q*): the
+ *   interval of diff (ratio) is NaN.  ratio_hat is the quotient as it comes (a_hat == 0: +-inf or NaN).
+ * Sums are fp64 in any order (a multiplicity times an fp32 value is exact): each within D * 2^-53 * sum |terms| of the exact sum;
+ * division and square root are correctly rounded.  No float atomics: the same inputs give the same bits.
+ *
+ * Three launches behind a memset: draws -> multiplicities W[r][i]; the replicate sums as the tiled product W . (a, b, valid) with fp64
+ * FMA, written series-major; one workgroup per series forms d* / q*, sorts them in LDS and reads the ranks.
+ * R <= ldc_paired_bootstrap_max_replicates() = 16384 (the keys of a series fill 128 KiB of LDS).
+ * workspace: ldc_paired_bootstrap_workspace_bytes(N, K, R, D) bytes (0: the sizes are not served), 16-byte aligned, no initialisation:
+ *   4 N RS rounded up to 256, plus 20 K RS, RS = R + 1 rounded up to 4.
+ * LDC_ERR_ARG: a null pointer, a non-positive size, ld < K, kind outside {0, 1}, tail_ppm outside [0, 500000) or a workspace that is
+ * too small; LDC_ERR_UNSUPPORTED: R above the cap, or more than 2^31 - 1 workgroups of 256 draws (R * D); LDC_ERR_ALIGN: a, b, draws or counts not 4-byte, stats
+ * not 8-byte or workspace not 16-byte aligned.  Nothing is launched or written on an error. */
+int ldc_paired_bootstrap_max_replicates(void);
+long long ldc_paired_bootstrap_workspace_bytes(int N, int K, int R, int D);
+int ldc_paired_bootstrap(const float* a, const float* b, long long ld, int N, int K, const int* draws, int R, int D, int kind,
+                         int tail_ppm, double* stats, int* counts, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

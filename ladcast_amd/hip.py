@@ -199,6 +199,9 @@ def _load():
         "ldc_field_moments": (I, [P, L, L, L, I, I, I, I, P, I, P, L, P]),
         "ldc_climatology_accumulate": (I, [P, L, L, L, I, I, I, I, P, I, P, P, P]),
         "ldc_climatology_smooth": (I, [P, P, P, I, I, I, I, L, P, P, P]),
+        "ldc_paired_bootstrap_max_replicates": (I, []),
+        "ldc_paired_bootstrap_workspace_bytes": (L, [I, I, I, I]),
+        "ldc_paired_bootstrap": (I, [P, P, L, I, I, P, I, I, I, I, P, P, P, L, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -668,6 +671,20 @@ def climatology_smooth(sum, count, weights, out, n_empty=None, *, n_days, n_hour
     _dev(sum, count, weights, out, n_empty)
     _check(lib.ldc_climatology_smooth(_p(sum), _p(count), _p(weights), int(weights.numel()), n_days, n_hours, C, plane, _p(out), _p(n_empty),
                                       _stream()), "ldc_climatology_smooth")
+
+
+def paired_bootstrap_workspace_bytes(N, K, R, D):
+    return int(lib.ldc_paired_bootstrap_workspace_bytes(N, K, R, D))
+
+
+def paired_bootstrap(a, b, draws, stats, counts, *, N, K, ld, R, D, kind, tail_ppm):
+    """stats (fp64 [K][8]) / counts (int32 [K][4]) of the paired bootstrap of the score arrays a, b (fp32, element (i, k) at i * ld + k) over
+    the replicates draws (device int32 [R][D], every value in [0, N): checked by the caller) (ladcast_hip.h: ldc_paired_bootstrap)"""
+    _dev(a, b, draws, stats, counts)
+    nbytes = paired_bootstrap_workspace_bytes(N, K, R, D)
+    ws = _workspace("paired_bootstrap", a.device, max(nbytes, 16), grow=True)
+    _check(lib.ldc_paired_bootstrap(_p(a), _p(b), ld, N, K, _p(draws), R, D, kind, tail_ppm, _p(stats), _p(counts), _p(ws), ws.numel() * 4,
+                                    _stream()), "ldc_paired_bootstrap")
 
 
 def compact_rope_table(cos, sin):
