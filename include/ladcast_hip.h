@@ -877,6 +877,37 @@ int ldc_derive_fields(const float* src, long long outer_stride, long long lead_s
                       const float* mean, const float* std_, float target_std, int n_outer, int L, int C, long long HW,
                       const ldc_derive_desc* desc, int D, float* out, long long out_outer_stride, long long out_lead_stride,
                       long long out_channel_stride, void* stream);
+/* Derived fields that need horizontal derivatives (additive under ABI 5; sphere_derive.hip): relative vorticity
+ * and divergence of a wind (u, v) = channels ch[0], ch[1] on a latitude-longitude grid, rows j < H at latitude phi_j, columns i < W at
+ * longitude 2 pi i / W (a full periodic circle).  Source addressing, slot, mean / std_ / target_std and the three out strides mean
+ * exactly what they mean for ldc_derive_fields, with HW = H * W and a contiguous (H, W) plane.  With
+ *   LDC_SPHERE_VORTICITY   (a, b) = (u, v)
+ *   LDC_SPHERE_DIVERGENCE  (a, b) = (-v, u)      D(u, v) = zeta(-v, u): one code path, the negation is exact
+ * de-normalised in fp32 and widened to double, jn = min(j + 1, H - 1), js = max(j - 1, 0), ie = (i + 1) mod W, iw = (i - 1 + W) mod W:
+ *   r[j] != 0:  dl = (b[j][ie] - b[j][iw]) * k;  dp = (a[jn][i] * c[jn] - a[js][i] * c[js]) * q[j];  out = (float)((dl - dp) * r[j])
+ *   r[j] == 0:  out = (float)((sum_i a[jp][i]) / W * pc[j]) for every i, jp = 1 for j == 0, else j - 1       (a pole row)
+ * every operation an IEEE double operation in this order (the file is built with -ffp-contract=off), one rounding to fp32.
+ * row_tables: DEVICE fp64 [4][H] = c, q, r, pc, made by the host (ladcast_amd.evaluate.derived.sphere_row_tables): c = cos phi (0 on a
+ * pole row), q = 1 / (phi[jn] - phi[js]), r = 1 / (R c) (0 on a pole row: that marks it), pc = the polar-cap factor; k = W / (4 pi).
+ * The kernel trusts the table.  One wave owns one row; a pole row's sum is taken by its wave: lane l adds elements l, l + 64, ... in
+ * double, then the xor butterfly 32 .. 1 - a fixed order, the same call gives the same bits.  A NaN input gives NaN at exactly the
+ * points whose stencil reads it (a whole pole row for a NaN anywhere in row jp); inf follows IEEE.  out must not overlap the planes
+ * that are read.  16-byte loads and stores when W % 4 == 0 and src, out and the six strides keep 16-byte alignment; a scalar path
+ * otherwise.  No atomics, no workspace, no scratch.
+ * LDC_ERR_ARG: a null src / row_tables / desc / out, mean without std_ or the reverse, a non-positive size, H < 2, W < 3, a negative
+ * stride, D outside 1 .. LDC_DERIVE_MAX_FIELDS, an unknown kind, a channel outside 0 .. C - 1; LDC_ERR_UNSUPPORTED: L or n_outer above
+ * 65535.  Nothing is launched on an error. */
+#define LDC_SPHERE_VORTICITY 0
+#define LDC_SPHERE_DIVERGENCE 1
+typedef struct ldc_sphere_desc {
+  int kind;
+  int ch[2]; /* u, v: indices into the C channels */
+} ldc_sphere_desc;
+int ldc_sizeof_sphere_desc(void);
+int ldc_derive_sphere(const float* src, long long outer_stride, long long lead_stride, long long channel_stride, const int* slot,
+                      const float* mean, const float* std_, float target_std, int n_outer, int L, int C, int H, int W,
+                      const double* row_tables, double k, const ldc_sphere_desc* desc, int D, float* out,
+                      long long out_outer_stride, long long out_lead_stride, long long out_channel_stride, void* stream);
 /* out[i] = np.nanmean over e < E of x[e*member_stride + i], i < n (fp32, the reference's ds.mean(dim="idx")): NaNs skipped, the
  * sum taken in member order, one division by the count (NaN where every member is NaN). */
 int ldc_track_nanmean(const float* x, long long member_stride, int E, long long n, float* out, void* stream);

@@ -8,7 +8,7 @@ _VALIDATE_NAMES = ("NpyLatentStore", "log_validation", "validate_initial_time") 
 _DENOISE_NAMES = ("denoising_loss", "evaluate_denoising_loss", "push_forward_plan")  # denoise_loss's, likewise
 _PRODUCTS_NAMES = ("products_of_latent_rollout",)  # products', likewise
 _ENERGY_NAMES = ("ENERGY_NAMES", "EnergyGroup", "empty_energy", "rollout_energy")  # energy's, likewise
-_DERIVED_NAMES = ("Derived", "derive_forecast", "derive_table", "derived_metadata", "parse_derived")  # derived's, likewise
+_DERIVED_NAMES = ("Derived", "SPHERE_KINDS", "derive_forecast", "derive_table", "derived_metadata", "parse_derived", "sphere_row_tables")  # derived's, likewise
 __all__ = ["VALIDATION_SCORE_NAMES", "ensemble_scores", "get_acc", "get_crps", "get_lat_weights_from_lat_tensor",  # module
            "get_normalized_lat_weights_based_on_cos", "pointwise_crps_skill", "pointwise_crps_spread", "rollout_reliability", "rollout_scores", "rollout_spectrum",  # also runs
            "validation_scores", "empty_products", "rollout_products", "EVENT_SCORE_NAMES", "Event", "empty_events", "event_scores", "rollout_events", "FSS_SCORE_NAMES", "empty_fss", "fss_scores", "rollout_fss", "NAMED_REGIONS", "REGIONAL_SCORE_NAMES",

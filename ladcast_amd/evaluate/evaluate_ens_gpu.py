@@ -14,8 +14,8 @@ xarray / zarr are not available: `--data_path` is a .npy of raw frames (N, C, H_
 `--start_date`; `--climatology_path` a .npy (366, 4, C, H_in, W) (day of year, hour 0 / 6 / 12 / 18).  `H_in == H + 1` crops row 0,
 the south pole.  `--reliability`, `--spectrum`, `--event` / `--event_anomaly` / `--fss_scales`, `--region` / `--region_box` and `--energy` /
 `--energy_group` add metrics that are not in the reference; what each computes and writes is stated by its class in `rollout_metrics`.
-`--derive NAME speed|diff|shear CHANNEL ...` appends a derived field (`derived`: wind speed, a difference, vertical shear) to the
-channels: every array gains a row, and `derived.json` names the fields.
+`--derive NAME speed|diff|shear|vorticity|divergence CHANNEL ...` appends a derived field (`derived`: wind speed, a difference, vertical
+shear, relative vorticity or divergence of a wind on the grid) to the channels: every array gains a row, and `derived.json` names the fields.
 Single rank only: splitting the initial times over ranks (`accelerate.split_between_processes`), more than 64
 members and the reference's commented-out `single_mse` are out of scope.
 """
@@ -119,7 +119,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     `derived`: a sequence of `derived.Derived(name, kind, channels)`; the D fields become channels C' .. C' + D - 1 of every result
     and of every option that names a channel (`events`, `energy_groups`, `energy_scales`).  Each decode batch is copied into the head
     of a (lead, ens, C' + D, H, W) buffer whose tail `derive_forecast` fills; truth and climatology become per-batch tables extended
-    the same way, the climatology of a `speed` / `shear` field NaN (so its `ens_acc` is NaN).  A field that reads `sst_channel` and an
+    the same way, the climatology of a `speed` / `shear` field NaN (so its `ens_acc` is NaN; `vorticity` / `divergence` are linear in the
+    wind and have a true climatology, on the rows `row_latitudes(H)`).  A field that reads `sst_channel` and an
     anomaly event on a `speed` / `shear` field are ValueErrors.  Without `derived` not one launch or copy is added."""
     from ..pipelines.io import load_latent_npy
     from ..pipelines.utils import _device_vector
@@ -251,8 +252,8 @@ def main(argv=None, score: Optional[Callable] = None):
     for cls in METRICS:
         cls.add_arguments(ap)
     ap.add_argument("--derive", nargs="+", action="append", default=[], metavar="NAME_KIND_CHANNELS",
-                    help="NAME speed|diff|shear CHANNEL [CHANNEL ...]: also score this derived field (speed: sqrt(a^2 + b^2) of channels a b; diff: a - b; "
-                         "shear: sqrt((a - c)^2 + (b - d)^2) of a b c d) as one more channel, which --event, --energy_group and the regional results then name; "
+                    help="NAME speed|diff|shear|vorticity|divergence CHANNEL [CHANNEL ...]: also score this derived field (speed: sqrt(a^2 + b^2) of channels a b; "
+                         "diff: a - b; shear: sqrt((a - c)^2 + (b - d)^2) of a b c d; vorticity, divergence: of the wind u v on the grid) as one more channel, which --event, --energy_group and the regional results then name; "
                          "may be given several times")
     ap.add_argument("--levels", type=int, nargs="+", default=LEVELS, help="pressure levels of the atmospheric variables, in channel order (--event channel names)")
     ap.add_argument("--num_atm_vars", type=int, default=NUM_ATM_VARS, help="leading variables that have one channel per level (--event channel names)")

@@ -14,7 +14,7 @@ the ensemble size - are all that leaves the device.  Decoded fields never exist 
 Channels are named as `validate_AR.column_names(track.VARIABLE_NAMES)` names them (`geopotential_level500`, `2m_temperature`, ...) or by
 index.  Per `latent_YYYYMMDDHH.npy` one `products_YYYYMMDDHH.npz` with `mean`, `std`, `min`, `max` (Cs, lead time, H, W), `quantiles`
 (Q, Cs, lead time, H, W) and `exceed` (P, Cs, lead time, H, W), and one `products.json` with the channel names, the quantiles, the
-thresholds with their direction and the ensemble size.  `--derive NAME speed|diff|shear CHANNEL ...` adds a derived field (`derived`) as one
+thresholds with their direction and the ensemble size.  `--derive NAME speed|diff|shear|vorticity|divergence CHANNEL ...` adds a derived field (`derived`) as one
 more channel - `--derive wind_speed_10m speed 10m_u_component_of_wind 10m_v_component_of_wind --exceed wind_speed_10m gt 17.2` maps the
 probability of gale-force wind - and `products.json` gains `derived`.  A threshold applies to its one channel: the other channels of that `exceed`
 plane hold NaN.  Single rank; `.npy` / `.npz` only.
@@ -163,7 +163,8 @@ def main(argv=None, products: Optional[Callable] = None):
     ap.add_argument("--exceed", nargs=3, action="append", default=[], metavar=("CHANNEL", "gt|lt", "VALUE"),
                     help=f"probability that CHANNEL is above (gt) / below (lt) VALUE, in physical units; up to {MAX_PRODUCT_THRESHOLDS} times")
     ap.add_argument("--derive", nargs="+", action="append", default=[], metavar="NAME_KIND_CHANNELS",
-                    help="NAME speed|diff|shear CHANNEL [CHANNEL ...]: a derived field (wind speed sqrt(a^2 + b^2), difference a - b, shear sqrt((a - c)^2 + (b - d)^2)) "
+                    help="NAME speed|diff|shear|vorticity|divergence CHANNEL [CHANNEL ...]: a derived field (wind speed sqrt(a^2 + b^2), difference a - b, shear sqrt((a - c)^2 + (b - d)^2), "
+                         "relative vorticity or divergence of the wind u v on the grid) "
                          "as one more channel, which --channels and --exceed then name; may be given several times")
     ap.add_argument("--total_num_steps", type=int, default=None, help="lead-time columns of the products (default: those of each file)")
     ap.add_argument("--crop_init", action="store_true", help="drop slot 0 of the latents (the initial condition)")

@@ -76,6 +76,13 @@ class DeriveDesc(Structure):  # ldc_derive_desc
     _fields_ = [("kind", c_int), ("ch", c_int * 4)]
 
 
+SPHERE_VORTICITY, SPHERE_DIVERGENCE = 0, 1  # LDC_SPHERE_*: fields of a wind (u, v) that need horizontal derivatives
+
+
+class SphereDesc(Structure):  # ldc_sphere_desc
+    _fields_ = [("kind", c_int), ("ch", c_int * 2)]
+
+
 class EventsDesc(Structure):  # ldc_events_desc
     _fields_ = [("n_events", c_int), ("channel", c_int * EVENTS_MAX), ("dir", c_int * EVENTS_MAX), ("anomaly", c_int * EVENTS_MAX),
                 ("thr", c_float * EVENTS_MAX)]
@@ -189,6 +196,8 @@ def _load():
         "ldc_track_gather": (I, [P, L, L, L, I, I, L, POINTER(c_int), I, P, P, F, P, I, I, P]),
         "ldc_sizeof_derive_desc": (I, []),
         "ldc_derive_fields": (I, [P, L, L, L, P, P, P, F, I, I, I, L, POINTER(DeriveDesc), I, P, L, L, L, P]),
+        "ldc_sizeof_sphere_desc": (I, []),
+        "ldc_derive_sphere": (I, [P, L, L, L, P, P, P, F, I, I, I, I, I, P, D, POINTER(SphereDesc), I, P, L, L, L, P]),
         "ldc_track_nanmean": (I, [P, L, I, L, P, P]),
         "ldc_track_storms": (I, [P, L, L, L, L, P, P, I, P, I, P, P, I, I, POINTER(c_int), I, I, P, P, P, P]),
         "ldc_track_local_min": (I, [P, L, P, P, I, P, I, P, P, P, I, P, P, P, P, P]),
@@ -219,6 +228,8 @@ def _load():
         raise RuntimeError("ldc_events_desc layout mismatch between header and binding")
     if lib.ldc_sizeof_derive_desc() != ctypes.sizeof(DeriveDesc):
         raise RuntimeError("ldc_derive_desc layout mismatch between header and binding")
+    if lib.ldc_sizeof_sphere_desc() != ctypes.sizeof(SphereDesc):
+        raise RuntimeError("ldc_sphere_desc layout mismatch between header and binding")
     return lib, sig
 
 
@@ -910,6 +921,34 @@ def derive_fields(src, out, desc, *, outer_stride, lead_stride, channel_stride, 
     _dev(src, out, slot, mean, std)
     _check(lib.ldc_derive_fields(_p(src), outer_stride, lead_stride, channel_stride, _p(slot), _p(mean), _p(std), float(target_std), n_outer, L, C,
                                  HW, desc, len(desc), _p(out), out_outer_stride, out_lead_stride, out_channel_stride, _stream()), "ldc_derive_fields")
+
+
+def sphere_desc(fields):
+    """the ldc_sphere_desc array for a sequence of (kind, (u, v)): kind SPHERE_VORTICITY or SPHERE_DIVERGENCE, the two wind channels.
+    Host only; the channel range is checked by the caller, who knows C."""
+    fs = [(int(k), [int(c) for c in ch]) for k, ch in fields]
+    if not 1 <= len(fs) <= DERIVE_MAX_FIELDS:
+        raise ValueError(f"{len(fs)} derived fields: ldc_derive_sphere takes 1 .. {DERIVE_MAX_FIELDS} per call")
+    arr = (SphereDesc * len(fs))()
+    for d, (kind, ch) in zip(arr, fs):
+        if kind not in (SPHERE_VORTICITY, SPHERE_DIVERGENCE) or len(ch) != 2:
+            raise ValueError(f"derived field (kind {kind}, channels {ch}): kind {SPHERE_VORTICITY} / {SPHERE_DIVERGENCE} reads the 2 channels u, v")
+        d.kind = kind
+        d.ch[0], d.ch[1] = ch
+    return arr
+
+
+def derive_sphere(src, out, desc, row_tables, k, *, outer_stride, lead_stride, channel_stride, n_outer, L, C, H, W, out_outer_stride,
+                  out_lead_stride, out_channel_stride, slot=None, mean=None, std=None, target_std=1.0):
+    """out[o][l][f] = field f of `desc` (`sphere_desc`): the vorticity or divergence of the inverse-normalised wind channels of src
+    (ladcast_hip.h: ldc_derive_sphere); row_tables: device fp64 (4, H) = c, q, r, pc and k, as `evaluate.derived.sphere_row_tables` makes
+    them; slot: device int32 [L] or None; the three out strides place the planes"""
+    _dev(src, out, row_tables, slot, mean, std)
+    if row_tables.dtype != torch.float64 or tuple(row_tables.shape) != (4, H) or not row_tables.is_contiguous():
+        raise ValueError(f"row_tables must be a contiguous fp64 (4, H) = (4, {H}) tensor")
+    _check(lib.ldc_derive_sphere(_p(src), outer_stride, lead_stride, channel_stride, _p(slot), _p(mean), _p(std), float(target_std), n_outer, L, C,
+                                 H, W, _p(row_tables), float(k), desc, len(desc), _p(out), out_outer_stride, out_lead_stride, out_channel_stride,
+                                 _stream()), "ldc_derive_sphere")
 
 
 def track_nanmean(x, out, *, member_stride, E, n):
