@@ -827,7 +827,14 @@ int ldc_rollout_energy(const float* forecast, long long member_stride, long long
  * launch.  The grid is two ASCENDING fp64 coordinate arrays built on the host exactly as the reference builds them
  * (lat = np.arange(-88.5, 90 + 1e-6, 1.5), 120 rows; lon = np.arange(0, 358.5 + 1e-6, 1.5), 240 columns); fields are fp32
  * [H][W] planes, row = latitude.  Box bounds are index ranges found by comparing against those arrays, and the coordinate
- * arithmetic rounds as Python's float ops do (Python's `%` included).  H, W <= LDC_TRACK_MAX_GRID.
+ * arithmetic rounds as Python's float ops do (Python's `%` included).  H, W <= LDC_TRACK_MAX_GRID.  Any strictly ascending
+ * finite grid is served (regional, irregular, one row or column, 0 and 360 both present); a non-finite centre finds nothing.
+ * The distance key that picks the closest surviving minimum, (la - lat0)**2 + ((lo - lon0 + 180) % 360 - 180)**2 in the
+ * reference, is computed as d * d, each product correctly rounded.  It equals the reference bit for bit whenever the
+ * coordinate differences square exactly (the default grid; any dyadic grid and centre).  Otherwise CPython's pow(d, 2) can
+ * differ from d * d by one rounding per term, which can decide only between candidates whose keys are within 2 ulp of each
+ * other; candidates with equal keys keep the reference's visiting order (rows ascending, then columns ascending, the small
+ * longitudes of a box that wraps first).
  * ------------------------------------------------------------------------- */
 #define LDC_TRACK_MAX_CHANNELS 8
 #define LDC_TRACK_MAX_BOXES 8 /* entries of inner_box_sizes */
@@ -839,7 +846,7 @@ int ldc_rollout_energy(const float* forecast, long long member_stride, long long
  * decoder's output in any layout with a contiguous HW plane: (B, C, T, HW) or the frame-major (B*T, C, HW) the decoder returns.
  * Same operations in the same order as ldc_chan_affine(inverse=1): bit-equal to decode_latent_ens(...)[:, channels].
  * `channels` is a HOST array of n_ch <= LDC_TRACK_MAX_CHANNELS indices (copied into the launch); mean / std are device vectors
- * indexed by channel. */
+ * indexed by channel.  LDC_ERR_UNSUPPORTED when n_ch is above its cap, B > 65535 or T * n_ch > 65535 (nothing is launched). */
 int ldc_track_gather(const float* x, long long sb, long long st, long long sc, int B, int T, long long HW, const int* channels,
                      int n_ch, const float* mean, const float* std_, float target_std, float* out, int T_total, int t_off,
                      void* stream);

@@ -160,8 +160,9 @@ __device__ MinResult find_local_min(const float* __restrict__ f, const double* l
     if (fabs(la - lat_lo) < 1e-6 || fabs(la - lat_hi) < 1e-6 || fabs(py_mod(lo - lon_s, 360.0)) < 1e-6 ||
         fabs(py_mod(lo - lon_e, 360.0)) < 1e-6)
       continue;
-    // (la - lat0)**2 + ((lo - lon0 + 180) % 360 - 180)**2: on the grid every difference is a multiple of 0.5 whose square is
-    // exact, so x * x equals CPython's pow(x, 2)
+    // (la - lat0)**2 + ((lo - lon0 + 180) % 360 - 180)**2 as d * d, each product correctly rounded.  On the default grid every
+    // difference is a multiple of 0.5 whose square is exact, so d * d equals CPython's pow(d, 2); the same holds on any dyadic
+    // grid and centre.  Elsewhere pow(d, 2) may differ from d * d by one rounding per term (ladcast_hip.h states the contract)
     const double dla = la - lat0, dlo = py_mod(lo - lon0 + 180.0, 360.0) - 180.0;
     const double key = dla * dla + dlo * dlo;
     if (key < best_key) {  // q grows per lane: the first of equal keys stays
@@ -290,7 +291,8 @@ extern "C" int ldc_track_gather(const float* x, long long sb, long long st, long
   LDC_CHECK_PTR(std_);
   LDC_CHECK_PTR(out);
   if (B <= 0 || T <= 0 || HW <= 0 || n_ch <= 0 || t_off < 0 || t_off + T > T_total) return LDC_ERR_ARG;
-  if (n_ch > LDC_TRACK_MAX_CHANNELS || B > 65535) return LDC_ERR_UNSUPPORTED;
+  // grid.y = T * n_ch and grid.z = B are limited to 65535 by the launch
+  if (n_ch > LDC_TRACK_MAX_CHANNELS || B > 65535 || static_cast<long long>(T) * n_ch > 65535) return LDC_ERR_UNSUPPORTED;
   ldc_track_channels ch;
   ch.n = n_ch;
   for (int k = 0; k < LDC_TRACK_MAX_CHANNELS; ++k) ch.idx[k] = k < n_ch ? channels[k] : 0;

@@ -131,7 +131,13 @@ def find_local_minima(fields: torch.Tensor, centers: Sequence[Tuple[float, float
                       field_idx: Optional[Sequence[int]] = None, *, lat=None, lon=None) -> List[Optional[Tuple[float, float, float]]]:
     """A batch of ``find_local_minimum`` calls in one launch (``ldc_track_local_min``).  fields: ``(F, H, W)`` fp32 device planes;
     query q searches ``fields[field_idx[q]]`` (default: q) around ``centers[q]`` with inner size ``inner_degs[q]``.  Each result is
-    ``(la, lo, v)`` or None, as the reference returns them."""
+    ``(la, lo, v)`` or None, as the reference returns them.  ``lat`` / ``lon``: any strictly ascending finite grid of up to
+    ``hip.TRACK_MAX_GRID`` entries per axis (default: the decoded 120 x 240 grid); a non-finite centre gives None.
+
+    The distance key that picks the closest surviving minimum is ``d * d`` per coordinate difference, each product correctly
+    rounded.  It equals the reference's ``d ** 2`` bit for bit whenever the differences square exactly (the default grid; any
+    dyadic grid and centre).  Otherwise it can differ by one rounding per term, which can decide only between candidates whose
+    keys are within 2 ulp of each other."""
     _require_device(fields)
     if fields.dim() != 3 or fields.dtype != torch.float32:
         raise ValueError("fields must be (F, H, W) float32")

@@ -1,6 +1,7 @@
 """Regenerate tests/golden/track_ref.npz from the reference's OWN tracking code (needs the reference tree at REF; not run by the tests).
 
     python tests/golden/make_track_golden.py [REFERENCE_ROOT]     (default: the reference checkout make_golden.py reads)
+    python tests/golden/make_track_golden.py --edges [REFERENCE_ROOT]     writes tests/golden/track_edge_ref.npz only (see edges())
 
 `round_to_grid`, `select_box`, `find_local_minimum` and `track_first_n_steps` are compiled from the syntax tree of
 ladcast/evaluate/track.py (the module imports cartopy, requests and xarray, which this tree does not have) and run on synthetic,
@@ -23,7 +24,8 @@ import numpy as np
 import pandas as pd
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = os.path.join(sys.argv[1] if len(sys.argv) > 1 else "/root/reference", "ladcast", "evaluate", "track.py")
+_ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+REF = os.path.join(_ARGS[0] if _ARGS else "/root/reference", "ladcast", "evaluate", "track.py")
 
 LAT = np.arange(-88.5, 90 + 1e-6, 1.5)
 LON = np.arange(0, 358.5 + 1e-6, 1.5)
@@ -194,11 +196,11 @@ def reference_functions():
 
 
 # ---- synthetic fields -------------------------------------------------------------------------------------------------------
-def lows(T, centres, depth, radius, background, rng=None, noise=0.0, cut=4.0):
+def lows(T, centres, depth, radius, background, rng=None, noise=0.0, cut=4.0, lat=LAT, lon=LON):
     """(T, H, W) float32: background + Gaussian lows moving along `centres` [(T, 2) per low], noise inside their support;
     rounded to whole units"""
-    la, lo = LAT[:, None], LON[None, :]
-    out = np.full((T, LAT.size, LON.size), background, dtype=np.float64)
+    la, lo = lat[:, None], lon[None, :]
+    out = np.full((T, lat.size, lon.size), background, dtype=np.float64)
     support = np.zeros(out.shape, dtype=bool)
     for path, d, r in zip(centres, depth, radius):
         for t in range(T):
@@ -216,6 +218,24 @@ def path(start, velocity, T):
     return [(start[0] + velocity[0] * t, (start[1] + velocity[1] * t) % 360) for t in range(T)]
 
 
+def make_dataset(t0, lat, lon, mslp, z700=None, lsm=None, members=None):
+    """the layout latent_ens_to_xarr builds: (idx,) time, prediction_timedelta, [level,] latitude, longitude"""
+    T = mslp.shape[-3]
+    coords = {"time": [t0], "prediction_timedelta": [timedelta(hours=6 * k) for k in range(T)], "level": [700], "latitude": lat,
+              "longitude": lon}
+    lead = ("time", "prediction_timedelta")
+    if members is not None:
+        coords["idx"] = list(range(members))
+        lead = ("idx",) + lead
+    v = {"mean_sea_level_pressure": DataArray(mslp[..., None, :, :, :] if members is None else mslp[:, None], lead + ("latitude", "longitude"), coords)}
+    if z700 is not None:
+        z = z700[None, :, None] if members is None else z700[:, None, :, None]
+        v["geopotential"] = DataArray(z, lead + ("level", "latitude", "longitude"), coords)
+    if lsm is not None:
+        v["land_sea_mask"] = DataArray(lsm, ("latitude", "longitude"), coords)
+    return Dataset(v)
+
+
 def main():
     ns = reference_functions()
     rng = np.random.default_rng(20181001)
@@ -223,21 +243,7 @@ def main():
     out = {"lat": LAT, "lon": LON}
 
     def dataset(mslp, z700=None, lsm=None, members=None):
-        """the layout latent_ens_to_xarr builds: (idx,) time, prediction_timedelta, [level,] latitude, longitude"""
-        T = mslp.shape[-3]
-        coords = {"time": [t0], "prediction_timedelta": [timedelta(hours=6 * k) for k in range(T)], "level": [700], "latitude": LAT,
-                  "longitude": LON}
-        lead = ("time", "prediction_timedelta")
-        if members is not None:
-            coords["idx"] = list(range(members))
-            lead = ("idx",) + lead
-        v = {"mean_sea_level_pressure": DataArray(mslp[..., None, :, :, :] if members is None else mslp[:, None], lead + ("latitude", "longitude"), coords)}
-        if z700 is not None:
-            z = z700[None, :, None] if members is None else z700[:, None, :, None]
-            v["geopotential"] = DataArray(z, lead + ("level", "latitude", "longitude"), coords)
-        if lsm is not None:
-            v["land_sea_mask"] = DataArray(lsm, ("latitude", "longitude"), coords)
-        return Dataset(v)
+        return make_dataset(t0, LAT, LON, mslp, z700, lsm, members)
 
     # -- tracks ---------------------------------------------------------------------------------------------------------------
     cases = []
@@ -356,5 +362,187 @@ def round_to_grid_py(v):
     return float(np.round(v / 1.5) * 1.5)
 
 
+# ---- the edge fixture: custom grids, off-grid centres, exact ties -----------------------------------------------------------
+EDGE_SEED = 20260117  # change the seed, never a condition, if the reference alone does not meet the assertions of edges()
+G6_FORMULAS = [(7919, 104729, 50), (0, 0, 1), (1, 3, 10 ** 9)]  # ((r * a + c * b) % m): plateaus of 50 values; constant 0; monotone
+
+
+def edge_grids(rng):
+    g3_lat, g3_lon = np.sort(rng.uniform(-89, 89, 37)), np.sort(rng.uniform(0, 360, 53))
+    assert np.all(np.diff(g3_lat) > 0) and np.all(np.diff(g3_lon) > 0)
+    return {
+        "G1": (LAT, LON),
+        "G2": (np.arange(-10.0, 10.5, 1.0), np.arange(100.0, 140.5, 1.0)),  # regional: does not close the circle
+        "G3": (g3_lat, g3_lon),  # irregular, non-dyadic
+        "G4a": (np.array([12.0]), LON),  # one row
+        "G4b": (LAT, np.array([181.5])),  # one column
+        "G5": (LAT, np.arange(0, 360 + 1e-6, 1.5)),  # 0 and 360 both present
+        "G6": (np.linspace(-60, 60, 1024), 0.25 * np.arange(1024)),  # the cap
+    }
+
+
+def edge_fields(lat, lon, rng):
+    """small integers as fp32: constant; plateaus of four values; monotone; plateaus with an all-NaN patch -> (fields, patch centre)"""
+    H, W = lat.size, lon.size
+    f1 = rng.integers(0, 4, (H, W)).astype(np.float32)
+    f2 = (np.arange(W, dtype=np.float32)[None, :] * 3 + np.arange(H, dtype=np.float32)[:, None]).astype(np.float32)
+    f3 = f1.copy()
+    r0, c0, nr, nc = H // 3, W // 3, max(1, H // 4), max(1, W // 4)
+    f3[r0 : r0 + nr, c0 : c0 + nc] = np.nan
+    return np.stack([np.full((H, W), 7.0, np.float32), f1, f2, f3]), (float(lat[r0 + nr // 2]), float(lon[c0 + nc // 2]))
+
+
+def edge_centres(lat, lon, rng, dyadic):
+    """(kind, lat0, lon0): on the grid, on cell centres, on the seam (unwrapped too), beside the first and last row, dyadic multiples of
+    1/64 off the grid, outside the grid.  On a non-dyadic grid the cell centres are moved to the next multiple of 1/64, so that no two
+    candidates are ALMOST equally far (the key precondition)."""
+    H, W = lat.size, lon.size
+    i, j = H // 2, W // 2
+    snap = (lambda v: float(v)) if dyadic else (lambda v: float(np.floor(v * 64) / 64))
+    mla, mlo = snap((lat[i] + lat[min(i + 1, H - 1)]) / 2), snap((lon[j] + lon[min(j + 1, W - 1)]) / 2)
+    gla, glo = float(lat[i]), float(lon[j])
+    out = [("grid", gla, glo), ("cell", mla, mlo), ("cell", mla, glo), ("cell", gla, mlo),
+           ("seam", 0.75 if lat[0] < 0.75 < lat[-1] else mla, 359.25), ("seam", mla, -0.75), ("seam", mla, 360.75), ("seam", gla, 359.25),
+           ("seam", gla, 0.0), ("seam", mla, 360.0),
+           ("row", float(lat[0]) - 0.75, glo), ("row", snap(float(lat[0]) + 0.75), mlo), ("row", float(lat[-1]) + 0.75, glo),
+           ("row", snap(float(lat[-1]) - 0.75), mlo)]
+    for _ in range(6):
+        out.append(("dyadic", float(np.round(rng.uniform(lat[0] - 2, lat[-1] + 2) * 64) / 64), float(np.round(rng.uniform(lon[0] - 2, lon[-1] + 2) * 64) / 64)))
+    out += [("outside", 95.0, glo), ("outside", -95.0, glo), ("outside", gla, -3.0), ("outside", gla, 363.0), ("outside", gla, 720.5)]
+    return out
+
+
+def edge_queries(name, lat, lon, patch, rng, dyadic):
+    """(field, lat0, lon0, inner).  Fields: 0 constant, 1 plateaus, 2 monotone, 3 plateaus with a NaN patch (G6: the three formulas)"""
+    cs = edge_centres(lat, lon, rng, dyadic)
+    q = []
+    if name == "G6":  # inner 0 and 1 only: a few hundred candidates per search
+        keep = [c for c in cs if c[0] in ("grid", "cell", "row")][:6] + [c for c in cs if c[0] == "dyadic"][:2] + [c for c in cs if c[0] == "outside"][:3]
+        for k, (_, la, lo) in enumerate(keep):
+            q += [(1, la, lo, 1), (0, la, lo, k % 2)]
+        q += [(1, keep[1][1], keep[1][2], 0), (2, keep[0][1], keep[0][2], 1), (2, keep[1][1], keep[1][2], 0)]
+        return q
+    for kind, la, lo in cs:
+        q += [(0, la, lo, 1), (0, la, lo, 12)]
+        if kind != "outside":
+            q += [(0, la, lo, 0), (1, la, lo, 5), (1, la, lo, 1)]
+        if kind in ("dyadic", "seam"):
+            q += [(1, la, lo, 12), (1, la, lo, 30), (3, la, lo, 5), (0, la, lo, 30)]
+    gla, glo = float(lat[lat.size // 2]), float(lon[lon.size // 2])
+    q += [(2, gla, glo, 5), (2, gla, glo, 12), (2, gla, glo, 0), (2, gla, glo, 30)]
+    q += [(3, patch[0], patch[1], 0), (3, patch[0], patch[1], 5), (3, patch[0], patch[1], 30)]
+    return q
+
+
+def edges():
+    """tests/golden/track_edge_ref.npz: find_local_minimum and track_first_n_steps of the reference on custom grids (edge_grids), with
+    centres off the grid and fields of small integers, so that plateaus and exact ties are the rule.  Asserts that every grid has both
+    outcomes, that enough searches are decided by the visiting order alone, and the two key preconditions of tests/track_oracle.py
+    (key_check) on every search.  track_ref.npz is not touched."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from tests import track_oracle as O
+
+    ns = reference_functions()
+    rng = np.random.default_rng(EDGE_SEED)
+    t0 = datetime(2018, 10, 1, 0)
+    grids = edge_grids(rng)
+    out = {"grid_names": np.array(list(grids)), "G6_formulas": np.array(G6_FORMULAS, dtype=np.int64)}
+    Q = {k: [] for k in ("grid", "field", "center", "inner", "found", "latlon", "value", "ties", "wrapped")}
+    n_tie = n_tie_wrapped = 0
+    for gi, (name, (lat, lon)) in enumerate(grids.items()):
+        dyadic = O.is_dyadic(lat, lon)
+        assert dyadic == (name not in ("G3", "G6")), name
+        out[f"{name}_lat"], out[f"{name}_lon"] = lat, lon
+        if name == "G6":
+            fields, patch = np.stack([O.formula_field(lat.size, lon.size, *f) for f in G6_FORMULAS]), None
+        else:
+            fields, patch = edge_fields(lat, lon, rng)
+            out[f"{name}_fields"] = fields
+        queries = edge_queries(name, lat, lon, patch, rng, dyadic)
+        found = ties = wrapped_ties = 0
+        for f, la0, lo0, inner in queries:
+            ds = Dataset({"v": DataArray(fields[f][None], ("time", "latitude", "longitude"), {"time": [t0], "latitude": lat, "longitude": lon})})
+            r = ns["find_local_minimum"](ds, "v", t0, (la0, lo0), inner)
+            fin = O.survivors(fields[f], (la0, lo0), inner, lat, lon)
+            n_min, problem = O.key_check(fin, (la0, lo0), dyadic and O.is_dyadic(la0, lo0))
+            assert problem is None, (name, f, la0, lo0, inner, problem)
+            assert (r is None) == (not fin) and (r is None or (r[0], r[1], r[2]) in fin), (name, f, la0, lo0, inner)
+            half_o = (inner + 3.0) / 2
+            wrapped = int((lo0 - half_o) % 360 > (lo0 + half_o) % 360)
+            for k, v in zip(Q, (gi, f, (la0, lo0), inner, int(r is not None), (r[0], r[1]) if r else (0.0, 0.0), r[2] if r else 0.0, n_min, wrapped)):
+                Q[k].append(v)
+            found += r is not None
+            ties += n_min >= 2
+            wrapped_ties += n_min >= 2 and wrapped
+        print(f"{name}: {lat.size} x {lon.size}, {len(queries)} queries, {found} found / {len(queries) - found} None, {ties} tie cases, "
+              f"{wrapped_ties} of them in a wrapped box")
+        assert 0 < found < len(queries), name  # both outcomes on every grid
+        n_tie, n_tie_wrapped = n_tie + ties, n_tie_wrapped + wrapped_ties
+    assert n_tie >= 12 and n_tie_wrapped >= 3, (n_tie, n_tie_wrapped)
+    for k, dt in (("grid", np.int32), ("field", np.int32), ("center", np.float64), ("inner", np.int32), ("found", np.int32), ("latlon", np.float64),
+                  ("value", np.float32), ("ties", np.int32), ("wrapped", np.int32)):
+        out[f"q_{k}"] = np.array(Q[k], dtype=dt)
+    # the constant field around (0.75, 359.25) with inner 1: four candidates equally far, the seam's small longitude visited first
+    hit = [i for i in range(len(Q["grid"])) if Q["grid"][i] == 0 and Q["field"][i] == 0 and Q["center"][i] == (0.75, 359.25) and Q["inner"][i] == 1]
+    assert hit and Q["latlon"][hit[0]] == (0.0, 0.0) and Q["ties"][hit[0]] == 4
+
+    # -- tracks (T = 4) ---------------------------------------------------------------------------------------------------------
+    T = 4
+    tracks = []
+    lat, lon = grids["G2"]
+    la, lo = lat[:, None], lon[None, :]
+    lsm2 = ((la >= 2) & (lo >= 122)).astype(np.float32)  # the start (1.5, 121.5) is the midpoint of four cells: only (2, 122) is land
+    m2 = lows(T, [path((2.0, 122.0), (0.9, 1.3), T)], [30], [2.0], 50, lat=lat, lon=lon)
+    z2 = lows(T, [path((1.0, 121.0), (-1.2, -0.8), T)], [20], [2.0], 90, lat=lat, lon=lon)
+    tracks.append(dict(grid="G2", mslp=m2, start=(1.4, 121.6), boxes=[7, 4, 1]))
+    tracks.append(dict(grid="G2", mslp=m2, z700=z2, lsm=lsm2, start=(1.4, 121.6), boxes=[7, 4, 1], enforce_msl=False))
+    lat, lon = grids["G3"]
+    m3 = lows(T, [path((20.0, 150.0), (4.0, 6.0), T)], [40], [9.0], 60, lat=lat, lon=lon)
+    z3 = lows(T, [path((22.0, 148.0), (-3.0, 5.0), T)], [25], [9.0], 80, lat=lat, lon=lon)
+    lsm3 = (rng.random((lat.size, lon.size)) < 0.5).astype(np.float32)
+    tracks.append(dict(grid="G3", mslp=m3, start=(20.3, 150.2), boxes=[30, 12, 5]))
+    tracks.append(dict(grid="G3", mslp=m3, z700=z3, lsm=lsm3, start=(20.3, 150.2), boxes=[30, 12, 5], enforce_msl=False))
+    lat, lon = grids["G5"]
+    m5 = lows(T, [path((15.0, 355.0), (0.6, 3.0), T)], [30], [2.5], 50, lat=lat, lon=lon)
+    tracks.append(dict(grid="G5", mslp=m5, start=(15.2, 355.3), boxes=[7, 4, 1]))
+    for i, c in enumerate(tracks):
+        lat, lon = grids[c["grid"]]
+        em = c.get("enforce_msl", True)
+        ds = make_dataset(t0, lat, lon, c["mslp"], c.get("z700"), c.get("lsm"))
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            trk = ns["track_first_n_steps"](t0, c["start"][0], c["start"][1], ds=ds, n_steps=T - 1, inner_box_sizes=c["boxes"], enforce_msl=em)
+        dyadic = O.is_dyadic(lat, lon)
+
+        def search(field, center, inner, la_, lo_):
+            _, problem = O.key_check(O.survivors(field, center, inner, la_, lo_), center, dyadic)
+            assert problem is None, (i, center, inner, problem)
+            return O.find_local_minimum(field, center, inner, la_, lo_)
+
+        O.track_first_n_steps(t0, c["start"][0], c["start"][1], c["mslp"], T - 1, c["boxes"], em, c.get("z700"), c.get("lsm"), lat, lon, search=search)
+        out[f"t{i}_grid"] = np.array(c["grid"])
+        out[f"t{i}_mslp"] = c["mslp"]
+        if not em:
+            out[f"t{i}_z700"], out[f"t{i}_lsm"] = c["z700"], c["lsm"]
+        out[f"t{i}_start"] = np.array(c["start"], dtype=np.float64)
+        out[f"t{i}_boxes"] = np.array(c["boxes"], dtype=np.int32)
+        out[f"t{i}_enforce_msl"] = np.array(int(em))
+        out[f"t{i}_track"] = np.array([(la_, lo_) for _, la_, lo_ in trk], dtype=np.float64)
+        moved = int((np.diff(out[f"t{i}_track"], axis=0) != 0).any(axis=1).sum())
+        print(f"track {i} on {c['grid']} (enforce_msl={em}): moved in {moved} of {T - 1} steps: {out[f't{i}_track'].tolist()}")
+    assert out["t4_track"][0, 1] > 300 and out["t4_track"][-1, 1] < 60  # the G5 track crosses 360 -> 0
+    assert not np.array_equal(out["t0_track"], out["t1_track"])  # the mask at the midpoint start decides (pandas' tie rule)
+    out["n_tracks"] = np.array(len(tracks))
+    path_out = os.path.join(HERE, "track_edge_ref.npz")
+    np.savez_compressed(path_out, **out)
+    nq = len(Q["grid"])
+    print(f"wrote {path_out}: {os.path.getsize(path_out) / 1e3:.0f} kB, {nq} queries ({int(out['q_found'].sum())} found), {n_tie} tie cases "
+          f"({n_tie_wrapped} in a wrapped box), {len(tracks)} tracks")
+    assert os.path.getsize(path_out) < 200e3
+
+
 if __name__ == "__main__":
-    main()
+    if "--edges" in sys.argv[1:]:
+        edges()
+    else:
+        main()

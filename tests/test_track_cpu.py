@@ -139,3 +139,113 @@ def test_caps_and_validation():
         TR.find_local_minimum(f[0], (15.0, 150.0), 7)
     with pytest.raises(RuntimeError):
         TR.find_local_minima(f, [(15.0, 150.0)], [7])
+
+
+# ---- the edge fixture: custom grids, off-grid centres, exact ties (tests/golden/make_track_golden.py --edges) ---------------
+EDGE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "track_edge_ref.npz")
+
+
+@pytest.fixture(scope="module")
+def edge():
+    return dict(np.load(EDGE))
+
+
+def edge_grid(edge, name):
+    return edge[f"{name}_lat"], edge[f"{name}_lon"]
+
+
+def edge_fields(edge, name):
+    """the (F, H, W) fp32 planes of one grid; the planes of the 1024 x 1024 grid are rebuilt from the stored formulas"""
+    if f"{name}_fields" in edge:
+        return edge[f"{name}_fields"]
+    lat, lon = edge_grid(edge, name)
+    return np.stack([O.formula_field(lat.size, lon.size, *f) for f in edge[f"{name}_formulas"]])
+
+
+def test_edge_fixture_holds_what_it_was_built_for(edge):
+    names = [str(n) for n in edge["grid_names"]]
+    assert names == ["G1", "G2", "G3", "G4a", "G4b", "G5", "G6"]
+    shapes = [tuple(c.size for c in edge_grid(edge, n)) for n in names]
+    assert shapes == [(120, 240), (21, 41), (37, 53), (1, 240), (120, 1), (120, 241), (1024, 1024)]
+    assert edge["G5_lon"][0] == 0.0 and edge["G5_lon"][-1] == 360.0
+    for gi, n in enumerate(names):
+        found = edge["q_found"][edge["q_grid"] == gi]
+        assert 0 < found.sum() < found.size, n  # both outcomes on every grid
+        assert O.is_dyadic(*edge_grid(edge, n)) == (n not in ("G3", "G6")), n
+    tie = (edge["q_ties"] >= 2) & (edge["q_found"] == 1)
+    assert tie.sum() >= 12 and (tie & (edge["q_wrapped"] == 1)).sum() >= 3
+    assert set(edge["q_inner"][edge["q_grid"] == names.index("G6")]) == {0, 1}
+    assert {0, 1, 5, 12, 30} <= set(edge["q_inner"].tolist())
+    assert os.path.getsize(EDGE) < 200e3
+
+
+def test_oracle_equals_every_edge_query_and_the_key_preconditions_hold(edge):
+    """tests/track_oracle.py on custom grids against the reference-made fixture, and - recomputed here - what the fixture's builder
+    asserted about the distance keys: on dyadic grids and centres every d * d equals d ** 2; elsewhere the winner's key is either
+    identical to a runner-up's under both or more than 4 ulp away"""
+    names = [str(n) for n in edge["grid_names"]]
+    cache = {n: (edge_grid(edge, n), edge_fields(edge, n)) for n in names}
+    for q in range(edge["q_found"].size):
+        (lat, lon), fields = cache[names[edge["q_grid"][q]]]
+        center, inner = tuple(float(v) for v in edge["q_center"][q]), int(edge["q_inner"][q])
+        fin = O.survivors(fields[edge["q_field"][q]], center, inner, lat, lon)
+        n_min, problem = O.key_check(fin, center, O.is_dyadic(lat, lon, center))
+        assert problem is None and n_min == edge["q_ties"][q], (q, problem, n_min)
+        r = O.find_local_minimum(fields[edge["q_field"][q]], center, inner, lat, lon)
+        if edge["q_found"][q]:
+            assert r is not None, q
+            assert (r[0], r[1]) == tuple(edge["q_latlon"][q]) and np.float32(r[2]).tobytes() == edge["q_value"][q].tobytes(), q
+        else:
+            assert r is None, q
+    # the issue's own example: four candidates equally far from (0.75, 359.25), the seam's small longitude is visited first
+    lat, lon = O.grid()
+    assert O.find_local_minimum(np.full((120, 240), 7.0, np.float32), (0.75, 359.25), 1, lat, lon) == (0.0, 0.0, 7.0)
+
+
+def test_oracle_equals_every_edge_track(edge):
+    for i in range(int(edge["n_tracks"])):
+        lat, lon = edge_grid(edge, str(edge[f"t{i}_grid"]))
+        em = bool(edge[f"t{i}_enforce_msl"])
+        mslp = edge[f"t{i}_mslp"]
+        dyadic = O.is_dyadic(lat, lon)
+
+        def search(field, center, inner, la, lo):
+            _, problem = O.key_check(O.survivors(field, center, inner, la, lo), center, dyadic)
+            assert problem is None, (i, center, inner, problem)
+            return O.find_local_minimum(field, center, inner, la, lo)
+
+        trk = O.track_first_n_steps(T0, *edge[f"t{i}_start"], mslp, mslp.shape[0] - 1, inner_box_sizes=list(edge[f"t{i}_boxes"]), enforce_msl=em,
+                                    z700=edge.get(f"t{i}_z700"), land_sea_mask=edge.get(f"t{i}_lsm"), lat=lat, lon=lon, search=search)
+        assert np.array_equal(np.array([(a, b) for _, a, b in trk]), edge[f"t{i}_track"]), i
+
+
+def test_nearest_index_is_pandas_rule_on_custom_grids(edge):
+    """midpoints of the regional grid (exact ties), the irregular grid, one-entry coordinates and points outside each of them"""
+    import pandas as pd
+
+    lat2, lon2 = edge_grid(edge, "G2")
+    lat3, lon3 = edge_grid(edge, "G3")
+    rng = np.random.default_rng(5)
+    cases = [(lat2, np.concatenate([lat2[:-1] + 0.5, lat2, [-10.5, -11.0, 10.5, 95.0, -95.0]])),
+             (lon2, np.concatenate([lon2[:-1] + 0.5, lon2, [99.5, 99.0, 140.5, -3.0, 363.0, 720.5]])),
+             (lat3, np.concatenate([(lat3[:-1] + lat3[1:]) / 2, lat3, rng.uniform(-95, 95, 40), [-95.0, 95.0]])),
+             (lon3, np.concatenate([(lon3[:-1] + lon3[1:]) / 2, lon3, rng.uniform(-5, 365, 40), [-3.0, 363.0, 720.5]])),
+             (np.array([12.0]), np.array([11.0, 12.0, 13.0, -95.0, 95.0])), (np.array([181.5]), np.array([-3.0, 181.5, 363.0, 720.5]))]
+    for coord, xs in cases:
+        want = pd.Index(coord).get_indexer(xs, method="nearest")
+        for x, w in zip(xs, want):
+            assert O.nearest_index(coord, float(x)) == int(w), (coord.size, x)
+
+
+def test_non_finite_centres_find_nothing(edge):
+    """NaN, +inf, -inf in either coordinate: the oracle (as the reference's masks: every comparison with NaN is False; inf % 360 is NaN)
+    returns None on every grid, which is what the GPU tests hold the kernel to"""
+    bad = [float("nan"), float("inf"), float("-inf")]
+    for name in ("G1", "G2", "G3", "G4a", "G4b", "G5"):
+        lat, lon = edge_grid(edge, name)
+        const = edge_fields(edge, name)[0]
+        for b in bad:
+            for center in ((b, float(lon[lon.size // 2])), (float(lat[lat.size // 2]), b), (b, b)):
+                for inner in (0, 1, 30):
+                    assert O.find_local_minimum(const, center, inner, lat, lon) is None, (name, center, inner)
+        assert O.find_local_minimum(const, (float(lat[lat.size // 2]), float(lon[lon.size // 2])), 30, lat, lon) is not None, name
