@@ -29,17 +29,8 @@ class KernelTimer:
         timer, orig = self, self._orig
         flops = lambda problems: sum(2.0 * p[0].d.M * p[0].d.N * p[0].d.K * p[0].d.batch for p in problems)  # noqa: E731
 
-        def gemm_grouped(problems, split_bf16=False):
-            # which kernel the C ABI dispatches to (gemm_streamk.hip, ldc_gemm_grouped_bf16x3): pre-split activations and K % 32 == 0 -> the
-            # 16x16x32 ring kernel; exact fp32: the ring kernel's TERMS = 0 instance when K % 32 == 0, else the register-staged stream-K kernel
-            if not split_bf16:
-                ring = all(p[0].d.K % 32 == 0 and p[0].d.ldw == p[0].d.K for p in problems) and os.environ.get("LDC_F32_RING", "1") != "0"
-                name = "gemm_bf16x3_v3_kernel<128, 0, false>" if ring else "gemm_streamk_kernel"
-            elif all(p[0].d.K % 32 == 0 for p in problems):
-                name = timer.v3_variant(problems) if all(p[0].d.flags & 1 for p in problems) else "gemm_streamk_bf16x3_kernel"
-            else:
-                name = "gemm_streamk_bf16x3_kernel"
-            return timer._bracket(name, flops(problems), orig["gemm_grouped"], problems, split_bf16=split_bf16)
+        def gemm_grouped(problems, split_bf16=False):  # named by the library's own plan of the call (ldc_gemm_grouped_plan)
+            return timer._bracket(hip.gemm_kernel_name(problems, split_bf16=split_bf16), flops(problems), orig["gemm_grouped"], problems, split_bf16=split_bf16)
 
         def gemm(A, W, C, **kw):
             return timer._bracket("gemm_nt_f32_kernel", 2.0 * kw["M"] * kw["N"] * kw["K"] * kw.get("batch", 1), orig["gemm"], A, W, C, **kw)
@@ -48,10 +39,10 @@ class KernelTimer:
             return timer._bracket("attn_fwd_f32_kernel", 4.0 * kw["B"] * kw["H"] * kw["S"] * kw["S"] * 128, orig["attn_fwd"], Q, K, V, O, **kw)
 
         def gemm_grouped_qkv(problems, epilogues, **kw):  # QKV projections with the attention-operand epilogue: the same kernel, same FLOPs
-            return timer._bracket(timer.v3_variant(problems), flops(problems), orig["gemm_grouped_qkv"], problems, epilogues, **kw)
+            return timer._bracket(hip.gemm_kernel_name(problems, epilogues, split_bf16=True), flops(problems), orig["gemm_grouped_qkv"], problems, epilogues, **kw)
 
-        def gemm_grouped_qkv_f32(problems, epilogues):  # the exact-fp32 QKV projection (RMSNorm + rotary epilogue): the TERMS = 0 ring instance
-            return timer._bracket("gemm_bf16x3_v3_kernel<128, 0, false>", flops(problems), orig["gemm_grouped_qkv_f32"], problems, epilogues)
+        def gemm_grouped_qkv_f32(problems, epilogues):  # the exact-fp32 QKV projection (RMSNorm + rotary epilogue)
+            return timer._bracket(hip.gemm_kernel_name(problems, epilogues), flops(problems), orig["gemm_grouped_qkv_f32"], problems, epilogues)
 
         def attn_fwd_split(Q, K, V, O, **kw):
             return timer._bracket("attn_fwd_split_kernel", 4.0 * kw["B"] * kw["H"] * kw["S"] * kw["S"] * 128, orig["attn_fwd_split"], Q, K, V, O, **kw)
@@ -59,14 +50,6 @@ class KernelTimer:
         for k, fn in (("gemm", gemm), ("attn_fwd", attn_fwd), ("gemm_grouped", gemm_grouped), ("gemm_grouped_qkv", gemm_grouped_qkv),
                       ("gemm_grouped_qkv_f32", gemm_grouped_qkv_f32), ("attn_fwd_split", attn_fwd_split)):
             setattr(hip, k, fn)
-
-    @staticmethod
-    def v3_variant(problems):
-        """the template instance gemm_v3_dispatch (csrc/gemm_bf16x3_v3.hip) launches for a grouped call - the kernel name rocprofv3 prints:
-        128-row tiles while 256-row tiles would number fewer than 400, TERMS = 1 in the single-term bf16 mode"""
-        t256 = sum(p[0].d.batch * -(-p[0].d.M // 256) * -(-p[0].d.N // 128) for p in problems)
-        terms = 1 if (problems[0][0].d.flags & 4) else 3
-        return f"gemm_bf16x3_v3_kernel<{128 if t256 < 400 else 256}, {terms}, false>"
 
     def uninstall(self):
         for k, fn in self._orig.items():

@@ -262,6 +262,31 @@ int ldc_gemm_grouped_bf16x3_qkv(const ldc_gemm_problem* problems, const ldc_qkv_
  * aligned): run ldc_gemm_grouped + ldc_qk_rmsnorm_rope. */
 int ldc_gemm_grouped_qkv_f32(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int n, void* workspace,
                              long long workspace_bytes, void* stream);
+/* (added since ABI 5, version unchanged) What a grouped call would run, without running it: ldc_gemm_grouped_plan returns the status
+ * ldc_gemm_grouped (split_bf16 = 0) | ldc_gemm_grouped_bf16x3 (1) would return for `problems` with a 16-byte aligned workspace of
+ * `workspace_bytes` - with epilogues != NULL: ldc_gemm_grouped_qkv_f32 | ldc_gemm_grouped_bf16x3_qkv - and on LDC_OK fills `out`.  It
+ * launches nothing and reads no data pointer: A / W / C / bias / ... are checked for NULL and alignment exactly as by the launch, so
+ * any addresses with the caller's alignment plan like the caller's buffers.  The same host code plans the launches themselves.
+ *   kernel    LDC_GEMM_KERNEL_RING: gemm_bf16x3_v3_kernel<tile_rows, terms, false> | LDC_GEMM_KERNEL_REGSTAGE: gemm_streamk_kernel
+ *             (terms 0) / gemm_streamk_bf16x3_kernel (terms 3), 128-row tiles
+ *   terms     0 exact fp32 | 1 single-term bf16 | 3 split bf16
+ *   launches  1, or n: a split-mode group without a k-aligned cut runs its problems one by one (launch l = problem l)
+ *   per launch l: tile_rows (128 | 256), workgroups, units (= (tile, k-step) pairs), tiles, and the cut: workgroup g runs units
+ *             [g units_per_group + min(g, units_rem), ...) (the register-staged kernels cut at g units / workgroups instead)
+ *   per problem p: its tile grid tile_rows_m x tile_cols_n (x batch), k_steps per tile, and super_row: the ring kernel walks the tiles in
+ *             bands of that many row tiles (= tile_rows_m: one band) */
+#define LDC_GEMM_KERNEL_RING 0
+#define LDC_GEMM_KERNEL_REGSTAGE 1
+typedef struct ldc_gemm_plan {
+  int kernel, terms, launches, reserved;
+  int tile_rows[LDC_GEMM_MAX_PROBLEMS], workgroups[LDC_GEMM_MAX_PROBLEMS];
+  long long units[LDC_GEMM_MAX_PROBLEMS], tiles[LDC_GEMM_MAX_PROBLEMS];
+  int units_per_group[LDC_GEMM_MAX_PROBLEMS], units_rem[LDC_GEMM_MAX_PROBLEMS];
+  int tile_rows_m[LDC_GEMM_MAX_PROBLEMS], tile_cols_n[LDC_GEMM_MAX_PROBLEMS], k_steps[LDC_GEMM_MAX_PROBLEMS], super_row[LDC_GEMM_MAX_PROBLEMS];
+} ldc_gemm_plan;
+int ldc_sizeof_gemm_plan(void);
+int ldc_gemm_grouped_plan(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epilogues, int n, int split_bf16,
+                          long long workspace_bytes, ldc_gemm_plan* out);
 int ldc_attn_qkv_prepare_split(float* Q, float* K, float* V, int B, int S, int H, int ld_qkv, long long qkv_bs, int split_row,
                                const float* wq0, const float* wk0, const float* cos0, const float* sin0, const float* wq1,
                                const float* wk1, const float* cos1, const float* sin1, float eps, void* stream);

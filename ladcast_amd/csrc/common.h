@@ -119,6 +119,45 @@ int ldc_conv_halo_dispatch(const float* X, const void* Wp, const float* bias, co
                            int ldx, int cout, int ldy, int ldr, int act, int in_fmt, int out_fmt, void* workspace, long long workspace_bytes,
                            void* stream);
 
+// gemm_plan.hip: the host planner of the grouped GEMMs.  Which kernel instance runs a group and how its (tile, k-step) units are cut
+// over the CUs is decided there and nowhere else; the launchers below only copy a plan into their kernel's argument struct.
+struct ldc_conv_params {  // the gathered conv as an implicit GEMM (ldc_sphere_conv_nhwc_split): 2^kshift k-steps per tap
+  int H, W, cin, ks, kshift;
+};
+struct ldc_gemm_problem_plan {  // what a launch adds to a problem's pointers and descriptor
+  int tm, tn, kt;
+  int rm;  // tile order: super-rows of rm row tiles (ring kernel)
+  long long unit0, tile0;  // first global unit / tile of this problem
+  int vec4;     // epilogue may use 16-byte accesses
+  int c_split;  // C in operand rows: LDC_FMT_SPLIT | LDC_FMT_BF16, 0 = fp32 rows
+  int qkv_heads, rope_row0;  // QKV projection epilogue: qkv_heads = 0 = ordinary epilogue
+  const float* qk_w[2];
+  const float* rope_cs;
+  float eps, qscale;
+};
+struct ldc_gemm_launch_plan {  // one kernel launch: G workgroups over U units; unit range g = [g upg + min(g, urem), ...)
+  ldc_gemm_problem_plan pr[LDC_GEMM_MAX_PROBLEMS];
+  long long tiles, U;
+  int G;
+  unsigned upg, urem;
+};
+struct ldc_gemm_group_plan {  // one call of a grouped entry point: launch l runs problems [first[l], first[l] + count[l])
+  int kernel;  // LDC_GEMM_KERNEL_RING | LDC_GEMM_KERNEL_REGSTAGE
+  int terms;   // 0 exact fp32 | 1 single-term bf16 | 3 split bf16
+  int launches;
+  int first[LDC_GEMM_MAX_PROBLEMS], count[LDC_GEMM_MAX_PROBLEMS], bm[LDC_GEMM_MAX_PROBLEMS];
+  ldc_gemm_launch_plan launch[LDC_GEMM_MAX_PROBLEMS];
+};
+// plan of one ring-kernel launch with bm-row tiles in arithmetic `terms`; cp != nullptr: the gathered conv.  Validates every problem and
+// the workspace in the order the launch statuses document; launches nothing
+int ldc_gemm_plan_ring(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int n, const void* workspace, long long workspace_bytes,
+                       int bm, int terms, const ldc_conv_params* cp, ldc_gemm_launch_plan* out);
+// gemm_bf16x3_v3.hip / gemm_streamk.hip: run one planned launch
+int ldc_gemm_ring_launch(const ldc_gemm_problem* problems, int n, const ldc_gemm_launch_plan& plan, int bm, int terms,
+                         const ldc_conv_params* cp, void* workspace, void* stream);
+int ldc_gemm_regstage_launch(const ldc_gemm_problem* problems, int n, const ldc_gemm_launch_plan& plan, bool split_bf16, void* workspace,
+                             void* stream);
+
 // Measurement switches (tile height / unit ranges / tile order / kernel choice forced from the environment) exist only in the A/B build
 // (`make ab` -> libladcast_hip_ab.so, loaded by tools/ through LDC_LIB_PATH); the shipped library reads no environment variable.
 #ifdef LDC_AB_BUILD

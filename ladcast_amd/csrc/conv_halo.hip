@@ -485,7 +485,7 @@ int ldc_conv_halo_dispatch(const float* X, const void* Wp, const float* bias, co
   int best_bm = 0, best_tw = 0, ksplit = 1;
   if (!halo_plan(B, H, W, cout, ldc_cdiv(cin, cpk), &best_bm, &best_tw, &ksplit)) return LDC_ERR_UNSUPPORTED;
   if (workspace == nullptr || workspace_bytes < LDC_GEMM_COUNTER_BYTES) return LDC_ERR_ARG;
-  // the argument checks of the gathered kernel's launcher (launch_v3, gemm_bf16x3_v3.hip), with its error codes: this path issues 16-byte
+  // the argument checks of the gathered kernel's planner (gemm_plan.hip), with its error codes: this path issues 16-byte
   // global -> LDS DMAs of X and Wp and takes `act` as a table index, so a misaligned view or a bad activation must not get past here
   LDC_CHECK_ALIGN16(Wp);
   LDC_CHECK_ALIGN16(workspace);

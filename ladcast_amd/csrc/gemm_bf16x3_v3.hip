@@ -135,7 +135,7 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(SKArgs a) {
     sg.k1 = (Q.kt - sg.k0 <= left) ? Q.kt : sg.k0 + static_cast<int>(left);
     // tile order (speed only): batch, then super-rows of rm row tiles, then column panels, row tile fastest.  An XCD owns a
     // contiguous run of units, i.e. about rm row panels x (tiles per XCD / rm) column panels: with rm = tm (one super-row)
-    // every XCD streams ALL of A and 1/8 of W; a squarer block fetches fewer bytes through the fabric (launch_v3 picks rm)
+    // every XCD streams ALL of A and 1/8 of W; a squarer block fetches fewer bytes through the fabric (gemm_plan.hip picks rm)
     const unsigned per_b = static_cast<unsigned>(Q.tm * Q.tn), tile_u = static_cast<unsigned>(sg.tile);
     const unsigned b_ = tile_u / per_b;
     const unsigned t_in = tile_u - b_ * per_b;
@@ -602,42 +602,16 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(SKArgs a) {
   LDC_STAMP(15)
 }
 
-struct ConvParams {
-  int H, W, cin, ks, kshift;
-};
-
-constexpr int LDC_SPLIT_GROUP = -100;  // internal: "launch this group's problems one by one" (gemm_v3_dispatch)
-
+// one planned launch (gemm_plan.hip: ldc_gemm_plan_ring): the plan and the caller's pointers into the kernel's argument struct
 template <int BM, int TERMS, bool CONV = false>
-int launch_v3(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int n, void* workspace, long long workspace_bytes,
-              void* stream, const ConvParams* cp = nullptr, bool may_split_group = false) {
-  constexpr int SLOT_FLOATS = BM * BN;
+int launch_v3(const ldc_gemm_problem* problems, int n, const ldc_gemm_launch_plan& plan, const ldc_conv_params* cp, void* workspace,
+              void* stream) {
   constexpr int STAGE_B = (BM + BN) * ROW_B;
-  constexpr int CUS = 256;  // one workgroup per CU
   SKArgs a{};
   a.np = n;
-  long long U = 0, tiles = 0;
   for (int i = 0; i < n; ++i) {
     const ldc_gemm_problem& q = problems[i];
-    LDC_CHECK_PTR(q.A);
-    LDC_CHECK_PTR(q.W);
-    LDC_CHECK_PTR(q.C);
-    const ldc_gemm_desc& d = q.d;
-    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch <= 0) return LDC_ERR_ARG;
-    if (d.K % (TERMS == 1 ? 2 * BK : BK)) return LDC_ERR_UNSUPPORTED;  // a 128-byte k-step: 64 plain-bf16 / 32 split / 32 fp32 values
-    if constexpr (TERMS == 0) {  // exact fp32: plain fp32 rows in, fp32 rows out, a contiguous [N][K] weight
-      if (d.flags != 0 || d.ldw != d.K) return LDC_ERR_UNSUPPORTED;
-    } else {
-      if (!(d.flags & LDC_GEMM_A_SPLIT)) return LDC_ERR_UNSUPPORTED;
-    }
-    LDC_CHECK_ALIGN16(q.A);
-    LDC_CHECK_ALIGN16(q.W);
-    if constexpr (TERMS == 0) {
-      if ((d.lda & 3) || (d.a_bs & 3)) return LDC_ERR_UNSUPPORTED;  // the caller falls back to the register-staged kernel
-    } else {
-      if ((d.lda & 7) || (d.a_bs & 7) || (reinterpret_cast<unsigned long long>(q.A) & 31ull)) return LDC_ERR_ALIGN;
-    }
-    if (d.act < LDC_ACT_NONE || d.act > LDC_ACT_RELU) return LDC_ERR_UNSUPPORTED;
+    const ldc_gemm_problem_plan& pp = plan.pr[i];
     DevProblem& P = a.pr[i];
     P.A = q.A;
     P.W = reinterpret_cast<const unsigned char*>(q.W);
@@ -645,161 +619,30 @@ int launch_v3(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int
     P.gate = q.gate;
     P.R = q.R;
     P.C = q.C;
-    P.d = d;
-    {
-      auto al16 = [](const void* q_) { return (reinterpret_cast<unsigned long long>(q_) & 15ull) == 0; };
-      bool v4 = (d.N % 4 == 0) && (d.ldc % 4 == 0) && (d.c_bs % 4 == 0) && al16(q.C);
-      if (q.bias) v4 = v4 && al16(q.bias);
-      if (q.gate) v4 = v4 && al16(q.gate) && (d.gate_bs % 4 == 0);
-      if (q.R) v4 = v4 && al16(q.R) && (d.ldr % 4 == 0) && (d.r_bs % 4 == 0);
-      P.vec4 = v4 ? 1 : 0;
-      P.c_split = (TERMS != 0 && (d.flags & LDC_GEMM_C_SPLIT)) ? (TERMS == 3 ? LDC_FMT_SPLIT : LDC_FMT_BF16) : 0;
-      // operand rows out: N % 4 == 0 (v4), the pad half of a last half-filled 8-column group is zeroed
-      if (P.c_split && !(v4 && d.ldc % 8 == 0 && d.ldc >= ((d.N + 7) & ~7) &&
-                         d.c_bs % 8 == 0 && (reinterpret_cast<unsigned long long>(q.C) & 31ull) == 0))
-        return LDC_ERR_ALIGN;
-    }
-    if (epi != nullptr && epi[i].heads > 0) {
-      const ldc_qkv_epilogue& e = epi[i];
-      auto al16 = [](const void* q_) { return (reinterpret_cast<unsigned long long>(q_) & 15ull) == 0; };
-      if (d.N != 3 * e.heads * BN || d.act != LDC_ACT_NONE || q.gate != nullptr || q.R != nullptr) return LDC_ERR_ARG;
-      if ((e.wq == nullptr) != (e.wk == nullptr) || e.reserved != nullptr || e.rope_row0 < 0) return LDC_ERR_ARG;
-      if constexpr (TERMS == 0) {  // plain fp32 rows out
-        if ((d.ldc & 3) || (d.c_bs & 3) || !al16(q.C)) return LDC_ERR_ALIGN;
-      } else {
-        if ((d.ldc & 7) || (d.c_bs & 7) || (reinterpret_cast<unsigned long long>(q.C) & 31ull)) return LDC_ERR_ALIGN;
-      }
-      if (!al16(e.wq) || !al16(e.wk) || !al16(e.rope) || (q.bias && !al16(q.bias))) return LDC_ERR_ALIGN;
-      P.qkv_heads = e.heads;
-      P.rope_row0 = e.rope_row0;
-      P.qk_w[0] = e.wq;
-      P.qk_w[1] = e.wk;
-      P.rope_cs = e.rope;
-      P.eps = e.eps;
-      P.qscale = e.qscale != 0.f ? e.qscale : 0.08838834764831845f * 1.4426950408889634f;
-    }
+    P.d = q.d;
+    P.tm = pp.tm; P.tn = pp.tn; P.kt = pp.kt; P.rm = pp.rm;
+    P.unit0 = pp.unit0;
+    P.tile0 = pp.tile0;
+    P.vec4 = pp.vec4;
+    P.c_split = pp.c_split;
+    P.qkv_heads = pp.qkv_heads;
+    P.rope_row0 = pp.rope_row0;
+    P.qk_w[0] = pp.qk_w[0];
+    P.qk_w[1] = pp.qk_w[1];
+    P.rope_cs = pp.rope_cs;
+    P.eps = pp.eps;
+    P.qscale = pp.qscale;
     if constexpr (CONV) {
       P.cH = cp->H; P.cW = cp->W; P.cin = cp->cin; P.ks = cp->ks; P.kshift = cp->kshift;
       // 16 zero bytes: the tail of the counter block (zeroed by ldc_gemm_grouped_workspace_init, written by nobody)
       P.zero16 = static_cast<const unsigned char*>(workspace) + LDC_GEMM_COUNTER_BYTES - 64;
     }
-    P.tm = ldc_cdiv(d.M, BM);
-    P.tn = ldc_cdiv(d.N, BN);
-    P.kt = d.K / (TERMS == 1 ? 2 * BK : BK);
-    P.unit0 = U;
-    P.tile0 = tiles;
-    {
-      // super-row height: an XCD's share is ~T8 = tiles / 8 consecutive tiles = rm row panels x T8 / rm column panels; per k-step
-      // it pulls rm * BM + (T8 / rm) * BN operand rows through the fabric -> minimum at rm = sqrt(T8 * BN / BM); super-rows of
-      // (nearly) equal height.  Only when the activation panel is what the one-super-row order over-fetches (every XCD streams all
-      // of A): measured (profiles/r02_c_gemm_tile_order_ab.log) 2250 x 1536 x 7680 -3.4 % time / -31 % fabric
-      // bytes and 18000 x 1536 x 7680 -10 %, but +3 % on 2250 x 4608 / 10752 x 1536, whose 14 MB A panel stays cached anyway.
-      // LDC_BF16X3_RM (measurement aid, read per call): force it; 0 = one super-row
-      P.rm = P.tm;
-      // (a conv's taps re-read the same pixels: its panel is M x ldx, and neighbouring row tiles share their halo rows)
-      const double a_bytes = CONV ? static_cast<double>(d.M) * d.lda * 4.0 : static_cast<double>(d.batch) * d.M * d.K * 4.0;
-      if (a_bytes >= 48e6) {
-        const double t8 = static_cast<double>(d.batch) * P.tm * P.tn / 8.0;
-        const double want = sqrt(t8 * BN / BM);
-        int nsr = static_cast<int>(P.tm / (want > 1.0 ? want : 1.0) + 0.5);
-        if (nsr < 1) nsr = 1;
-        if (nsr > P.tm) nsr = P.tm;
-        P.rm = ldc_cdiv(P.tm, nsr);
-      }
-      if (const char* e = LDC_AB_GETENV("LDC_BF16X3_RM")) {
-        const int f = atoi(e);
-        if (f >= 0) P.rm = (f == 0 || f > P.tm) ? P.tm : f;
-      }
-    }
-    const long long t = static_cast<long long>(d.batch) * P.tm * P.tn;
-    tiles += t;
-    U += t * P.kt;
   }
-  if (tiles > LDC_GEMM_COUNTER_BYTES / 4 - 16) return LDC_ERR_UNSUPPORTED;  // in-launch reduction only; last 64 B: zero page
-  const long long slot_bytes = SLOT_FLOATS * static_cast<long long>(sizeof(float));
-  // grid size: (phase-aligned divisor of tiles * s when every problem has the same k-depth)
-  long long G = CUS;
-  {
-    bool same_kt = true;
-    for (int i = 1; i < n; ++i) same_kt = same_kt && (a.pr[i].kt == a.pr[0].kt);
-    long long best = 0;
-    if (same_kt) {
-      const int kt = a.pr[0].kt;
-      // more workgroups win unless they are bought with many more pieces per tile (a hand-off each): 2 % per extra split factor.
-      // 288 tiles x 320 k-steps (the 1.6B model's single-block out projection): 192 ranges at s = 2, 240 at s = 5 - 279 -> 269 us
-      double best_score = 0.0;
-      for (int sfac = 1; sfac <= 8; ++sfac) {
-        if (kt % sfac || (sfac > 1 && kt / sfac < 8)) continue;  // whole tiles (sfac 1) at any depth
-        const long long items = tiles * sfac;
-        long long gd = items < CUS ? items : CUS;
-        while (gd > 1 && items % gd) --gd;
-        const double score = static_cast<double>(gd) * (1.0 - 0.02 * (sfac - 1));
-        if (score > best_score) {
-          best_score = score;
-          best = gd;
-        }
-      }
-    }
-    long long few = 0;  // few tiles (the 84-column output head: 15 tiles): aligned split-K over more workgroups
-    if (same_kt && best < 160) {
-      const int kt = a.pr[0].kt;
-      for (int sfac = 8; sfac >= 2; --sfac)
-        if (kt % sfac == 0 && kt / sfac >= 8 && tiles * sfac <= CUS) {
-          few = tiles * sfac;
-          break;
-        }
-    }
-    // Round 4: a GROUP whose tile count has no k-aligned cut onto >= 160 workgroups (1.6B dual blocks: (15 + 4) x 16 = 304 tiles of
-    // k-depth 2^j - every aligned grid is a multiple of 19 that divides 304 s: 152) used to take the unaligned ranges below, which cost
-    // the split modes 40 % (out / down projection of the 1.6B dual block: 205 / 213 TFLOP/s).  Its problems one by one cut well
-    // (pred: 240 tiles = 240 workgroups; cond: 64 tiles x 4 k-pieces = 256): the dispatcher launches them separately.
-    if (may_split_group && TERMS != 0 && n > 1 && best < 160 && few == 0) return LDC_SPLIT_GROUP;
-    if (best >= 160) {
-      G = best;
-    } else if (few > 0) {
-      G = few;  // measured on 1800 x 84 x 1536: 24.7 us at the stream-K default (36 ranges), 18.0 at 90
-    } else {
-      const double kt_avg = static_cast<double>(U) / static_cast<double>(tiles);
-      long long umin = static_cast<long long>(sqrt(kt_avg * 8.0) + 0.5);
-      if (umin < 1) umin = 1;
-      const long long gmax = U / umin > 0 ? U / umin : 1;
-      if (gmax < G) G = gmax;
-    }
-  }
-  if constexpr (TERMS == 0) {  // (the DCAE's fp32 convs too: 8.09 / 8.83 -> 7.73 / 8.41 ms per frame, profiles/r04_l_dcae_unit_ranges_ab.txt; the split modes lose 10 % with it)
-    // exact fp32 (round 4): ALWAYS one unit range per CU, cut wherever U / 256 falls.  The fp32 k-step is matrix-pipe bound (5x the split
-    // kernel's MFMA time per k-step), so the L2 lockstep that made unaligned ranges 40 % slower in the split mode does not matter here and
-    // the chip is not at its power cap: idle CUs cost their full share.  375M in fp32 mode, same box: 111.3 -> 118.5 TFLOP/s per GEMM launch,
-    // 2.82 -> 2.96 member-steps/s (aligned 240 / 248 ranges: 111.6 / 115.0; profiles/r04_k_fp32_unit_ranges.txt)
-    if (U >= 4 * CUS) G = CUS;
-  }
-  static const char* const force_g = LDC_AB_GETENV("LDC_BF16X3_G");  // measurement aid (read once): force the number of unit ranges
-  if (force_g) {
-    const long long g_ = atoll(force_g);
-    if (g_ > 0 && g_ <= CUS) G = g_;
-  }
-  if (U < G) G = U;
-  if (workspace == nullptr) return LDC_ERR_ARG;
-  if (workspace_bytes < LDC_GEMM_COUNTER_BYTES + 2 * slot_bytes) return LDC_ERR_ARG;
-  {
-    const long long fit = (workspace_bytes - LDC_GEMM_COUNTER_BYTES) / (2 * slot_bytes);
-    if (fit < G) G = fit;
-  }
-  LDC_CHECK_ALIGN16(workspace);
-  if (U >= (1LL << 31)) return LDC_ERR_UNSUPPORTED;  // 32-bit unit arithmetic in the kernel
-#ifdef LDC_AB_BUILD
-  {  // A/B build only: LDC_GEMM_DEBUG_G=1 prints every launch's cut (n problems, tiles, k-depth, tile rows, unit ranges, units per range)
-    static const bool dbg = getenv("LDC_GEMM_DEBUG_G") != nullptr;
-    if (dbg)
-      fprintf(stderr, "ldc_gemm cut: terms %d conv %d n %d tiles %lld kt0 %d BM %d G %lld U %lld %s\n", TERMS, int(CONV), n, tiles, a.pr[0].kt, BM, G, U,
-              (U % G == 0 && (U / G) % a.pr[0].kt == 0) ? "whole tiles" : (U % G == 0 ? "equal ranges" : "UNALIGNED"));
-  }
-#endif
-  a.G = static_cast<int>(G);
-  a.U = U;
-  a.upg = static_cast<unsigned>(U / G);
-  a.urem = static_cast<unsigned>(U % G);
-  a.tiles = tiles;
+  a.G = plan.G;
+  a.U = plan.U;
+  a.upg = plan.upg;
+  a.urem = plan.urem;
+  a.tiles = plan.tiles;
   a.ws = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + LDC_GEMM_COUNTER_BYTES);
   a.counters = static_cast<unsigned*>(workspace);
   const size_t lds = NSTAGE * STAGE_B + 8 * 1024;  // ring + one 1 KiB dump slot per wave
@@ -815,97 +658,24 @@ int launch_v3(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int
 
 }  // namespace
 
-// returns LDC_ERR_UNSUPPORTED when a problem does not fit this kernel (caller falls back to the register-staged kernel of gemm_streamk.hip)
-static int gemm_v3_dispatch(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int n, void* workspace,
-                            long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(problems);
-  if (n <= 0 || n > MAXP) return LDC_ERR_ARG;
-  long long tiles256 = 0;
-  for (int i = 0; i < n; ++i) {
-    const ldc_gemm_desc& d = problems[i].d;
-    if (d.M <= 0 || d.N <= 0 || d.batch <= 0) return LDC_ERR_ARG;
-    if (!(d.flags & LDC_GEMM_A_SPLIT)) return LDC_ERR_UNSUPPORTED;
-    if (((d.flags ^ problems[0].d.flags) & LDC_GEMM_BF16_1TERM) != 0) return LDC_ERR_ARG;  // one arithmetic per launch
-    tiles256 += static_cast<long long>(d.batch) * ldc_cdiv(d.M, 256) * ldc_cdiv(d.N, BN);
-  }
-  // half-height tiles while 256-row tiles would not fill the chip twice over (both heights run 8 waves here, so the
-  // half-height tile costs no MFMA efficiency, only twice the W traffic per FLOP); LDC_BF16X3_BM forces one
-  static const char* const force_thr = LDC_AB_GETENV("LDC_BF16X3_SMALL_TILES");  // measurement aid, read once: the cross-over below
-  bool small = tiles256 < (force_thr ? atoll(force_thr) : 400);  // measured cross-over on the 375M model launches (tools/gemm_sustained.py, both heights forced)
-  static const char* const force_bm = LDC_AB_GETENV("LDC_BF16X3_BM");  // measurement aid, read once
-  if (force_bm) small = (atoi(force_bm) == 128);
-  const bool one = (problems[0].d.flags & LDC_GEMM_BF16_1TERM) != 0;
-  auto launch = [&](const ldc_gemm_problem* pr, const ldc_qkv_epilogue* ep, int cnt, bool sm, bool may_split) {
-    if (one)
-      return sm ? launch_v3<128, 1>(pr, ep, cnt, workspace, workspace_bytes, stream, nullptr, may_split)
-                : launch_v3<256, 1>(pr, ep, cnt, workspace, workspace_bytes, stream, nullptr, may_split);
-    return sm ? launch_v3<128, 3>(pr, ep, cnt, workspace, workspace_bytes, stream, nullptr, may_split)
-              : launch_v3<256, 3>(pr, ep, cnt, workspace, workspace_bytes, stream, nullptr, may_split);
-  };
-  const int st = launch(problems, epi, n, small, true);
-  if (st != LDC_SPLIT_GROUP) return st;
-  // (no partial output on a bad argument: launch_v3 returns LDC_SPLIT_GROUP only after it has validated EVERY problem of the group - the
-  // per-problem checks run before the cut is chosen - and the workspace checks that follow it fail on the first single launch, before
-  // anything has been queued)
-  for (int i = 0; i < n; ++i) {  // the group has no good aligned cut: its problems one after the other (independent; same stream)
-    const ldc_gemm_desc& d = problems[i].d;
-    bool sm = static_cast<long long>(d.batch) * ldc_cdiv(d.M, 256) * ldc_cdiv(d.N, BN) < (force_thr ? atoll(force_thr) : 400);
-    if (force_bm) sm = (atoi(force_bm) == 128);
-    const int sti = launch(problems + i, epi ? epi + i : nullptr, 1, sm, false);
-    if (sti != LDC_OK) return sti;
-  }
-  return LDC_OK;
-}
-
-// exact-fp32 grouped GEMM on the ring kernel (TERMS = 0); LDC_ERR_UNSUPPORTED -> the caller (ldc_gemm_grouped, gemm_streamk.hip) runs
-// its register-staged stream-K kernel instead (K % 32 != 0, strided weights, unaligned rows)
-static int gemm_f32_ring(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int n, void* workspace, long long workspace_bytes,
-                         void* stream) {
-  LDC_CHECK_PTR(problems);
-  if (n <= 0 || n > MAXP) return LDC_ERR_ARG;
-  for (int i = 0; i < n; ++i)  // the caller's choice (include/ladcast_hip.h): this launch stays on the register-staged kernel
-    if (problems[i].d.flags & LDC_GEMM_F32_REGSTAGE) return LDC_ERR_UNSUPPORTED;
-  auto al16 = [](const void* q_) { return q_ != nullptr && (reinterpret_cast<unsigned long long>(q_) & 15ull) == 0; };
-  // what the register-staged kernel accepts and this one does not goes there, not back to the caller as an error
-  if (!al16(workspace) || workspace_bytes < LDC_GEMM_COUNTER_BYTES + 2ll * 256 * BN * static_cast<long long>(sizeof(float)))
-    return LDC_ERR_UNSUPPORTED;
-  for (int i = 0; i < n; ++i) {
-    const ldc_gemm_desc& d = problems[i].d;
-    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch <= 0) return LDC_ERR_ARG;
-    if (!al16(problems[i].A) || !al16(problems[i].W)) return LDC_ERR_UNSUPPORTED;
-  }
-  // 128-row tiles only: a tile is 2.7x the split kernel's MFMA time, so balance matters more than the halved W traffic per FLOP of
-  // the 256-row tile (375M model in fp32 mode, same box: 113.6 TFLOP/s against 111.0 with 256 rows forced; profiles/r03_j_*)
-#ifdef LDC_AB_BUILD
-  static const char* const force_bm = getenv("LDC_F32_RING_BM");  // A/B build only: 256-row tiles for the exact-fp32 GEMMs
-  if (force_bm && atoi(force_bm) == 256) return launch_v3<256, 0>(problems, epi, n, workspace, workspace_bytes, stream);
+// the kernel instance of a planned launch: tile height x arithmetic x (GEMM | gathered conv)
+int ldc_gemm_ring_launch(const ldc_gemm_problem* problems, int n, const ldc_gemm_launch_plan& plan, int bm, int terms,
+                         const ldc_conv_params* cp, void* workspace, void* stream) {
+  const bool sm = bm == 128;
+  if (cp == nullptr) {
+    if (terms == 1)
+      return sm ? launch_v3<128, 1>(problems, n, plan, cp, workspace, stream) : launch_v3<256, 1>(problems, n, plan, cp, workspace, stream);
+    if (terms == 3)
+      return sm ? launch_v3<128, 3>(problems, n, plan, cp, workspace, stream) : launch_v3<256, 3>(problems, n, plan, cp, workspace, stream);
+#ifdef LDC_AB_BUILD  // (the planner gives exact fp32 256-row tiles in the A/B build only: LDC_F32_RING_BM)
+    if (!sm) return launch_v3<256, 0>(problems, n, plan, cp, workspace, stream);
 #endif
-  return launch_v3<128, 0>(problems, epi, n, workspace, workspace_bytes, stream);
-}
-
-int ldc_gemm_grouped_f32_ring(const ldc_gemm_problem* problems, int n, void* workspace, long long workspace_bytes, void* stream) {
-  return gemm_f32_ring(problems, nullptr, n, workspace, workspace_bytes, stream);
-}
-
-// exact-fp32 QKV projection with per-head RMSNorm + rotary embedding as its epilogue, plain fp32 rows out (include/ladcast_hip.h);
-// LDC_ERR_UNSUPPORTED (K % 32 != 0, strided weights, unaligned rows): run ldc_gemm_grouped and ldc_qk_rmsnorm_rope instead
-extern "C" int ldc_gemm_grouped_qkv_f32(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int n, void* workspace,
-                                        long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(epi);
-  return gemm_f32_ring(problems, epi, n, workspace, workspace_bytes, stream);
-}
-
-int ldc_gemm_grouped_bf16x3_v3(const ldc_gemm_problem* problems, int n, void* workspace, long long workspace_bytes,
-                               void* stream) {
-  return gemm_v3_dispatch(problems, nullptr, n, workspace, workspace_bytes, stream);
-}
-
-// QKV projection with the attention operand rows as output (include/ladcast_hip.h); only this kernel has that epilogue:
-// LDC_ERR_UNSUPPORTED (K % 32 != 0, fp32 activations) means "run the plain GEMM and ldc_attn_qkv_prepare_split instead"
-extern "C" int ldc_gemm_grouped_bf16x3_qkv(const ldc_gemm_problem* problems, const ldc_qkv_epilogue* epi, int n, void* workspace,
-                                           long long workspace_bytes, void* stream) {
-  LDC_CHECK_PTR(epi);
-  return gemm_v3_dispatch(problems, epi, n, workspace, workspace_bytes, stream);
+    return launch_v3<128, 0>(problems, n, plan, cp, workspace, stream);
+  }
+  if (terms == 0) return launch_v3<128, 0, true>(problems, n, plan, cp, workspace, stream);  // (the exact-fp32 conv has 128-row tiles only)
+  if (terms == 1)
+    return sm ? launch_v3<128, 1, true>(problems, n, plan, cp, workspace, stream) : launch_v3<256, 1, true>(problems, n, plan, cp, workspace, stream);
+  return sm ? launch_v3<128, 3, true>(problems, n, plan, cp, workspace, stream) : launch_v3<256, 3, true>(problems, n, plan, cp, workspace, stream);
 }
 
 // SphereConv2d (dense, stride 1, k = 3 / 5; k = 1: pointwise conv / Linear over pixel rows) as an implicit GEMM on the pre-split kernel.
@@ -936,7 +706,7 @@ extern "C" int ldc_sphere_conv_nhwc_split(const float* X, const void* Wp, const 
   if (M > 0x7fffffffLL) return LDC_ERR_UNSUPPORTED;
   const bool one = in_fmt == LDC_FMT_BF16;
   const int cpk = one ? 2 * BK : BK;  // channels per k-step
-  ConvParams cp{H, W, cin, ksize, 0};
+  ldc_conv_params cp{H, W, cin, ksize, 0};
   int ktpt = ldc_cdiv(cin, cpk);  // k-steps per tap, rounded up to a power of two (the kernel shifts instead of dividing)
   while ((1 << cp.kshift) < ktpt) ++cp.kshift;
   ktpt = 1 << cp.kshift;
@@ -956,11 +726,16 @@ extern "C" int ldc_sphere_conv_nhwc_split(const float* X, const void* Wp, const 
   q.d.ldr = ldr;
   q.d.act = act;
   q.d.flags = LDC_GEMM_A_SPLIT | (out_fmt != LDC_FMT_F32 ? LDC_GEMM_C_SPLIT : 0) | (one ? LDC_GEMM_BF16_1TERM : 0);
+  auto run = [&](int bm, int terms) {  // plan the one launch, then run the plan
+    ldc_gemm_launch_plan plan;
+    const int st = ldc_gemm_plan_ring(&q, nullptr, 1, workspace, workspace_bytes, bm, terms, &cp, &plan);
+    return st != LDC_OK ? st : ldc_gemm_ring_launch(&q, 1, plan, bm, terms, &cp, workspace, stream);
+  };
   if (in_fmt == LDC_FMT_F32) {
     // the exact-fp32 variant of the ring kernel (TERMS = 0: v_mfma_f32_16x16x4_f32 on plain fp32 operand rows) with the same conv gather;
     // 128-row tiles only, as for the fp32 GEMMs (a tile is 2.7x the split kernel's MFMA time: balance beats the halved W traffic)
     q.d.flags = 0;
-    return launch_v3<128, 0, true>(&q, nullptr, 1, workspace, workspace_bytes, stream, &cp);
+    return run(128, 0);
   }
   if (ksize == 3) {  // round 5: the halo-staged kernel (conv_halo.hip) where it serves the shape
     static const char* const halo_sw = LDC_AB_GETENV("LDC_CONV_HALO");  // measurement aid (A/B build): 0 = never
@@ -975,9 +750,5 @@ extern "C" int ldc_sphere_conv_nhwc_split(const float* X, const void* Wp, const 
   // 128; 504 -> 504 at 60 x 120 (116 tiles): 122 / 111; four frames of it (464): 350 / 437.  LDC_CONV_SMALL_TILES: measurement aid
   static const char* const force_thr = LDC_AB_GETENV("LDC_CONV_SMALL_TILES");
   const bool small = tiles256 < (force_thr ? atoll(force_thr) : 200);
-  if (one)
-    return small ? launch_v3<128, 1, true>(&q, nullptr, 1, workspace, workspace_bytes, stream, &cp)
-                 : launch_v3<256, 1, true>(&q, nullptr, 1, workspace, workspace_bytes, stream, &cp);
-  return small ? launch_v3<128, 3, true>(&q, nullptr, 1, workspace, workspace_bytes, stream, &cp)
-               : launch_v3<256, 3, true>(&q, nullptr, 1, workspace, workspace_bytes, stream, &cp);
+  return run(small ? 128 : 256, one ? 1 : 3);
 }

@@ -471,26 +471,14 @@ extern "C" int ldc_gemm_grouped_workspace_init(void* workspace, long long worksp
   return e == hipSuccess ? LDC_OK : -(1000 + static_cast<int>(e));
 }
 
-static int gemm_grouped_impl(const ldc_gemm_problem* problems, int n, void* workspace, long long workspace_bytes,
-                             void* stream, bool split_bf16) {
-  LDC_CHECK_PTR(problems);
-  if (n <= 0 || n > MAXP) return LDC_ERR_ARG;
+// one planned launch of the register-staged kernels (gemm_plan.hip chooses them and their G)
+int ldc_gemm_regstage_launch(const ldc_gemm_problem* problems, int n, const ldc_gemm_launch_plan& plan, bool split_bf16, void* workspace,
+                             void* stream) {
   SKArgs a{};
   a.np = n;
-  long long U = 0, tiles = 0;
   for (int i = 0; i < n; ++i) {
     const ldc_gemm_problem& q = problems[i];
-    LDC_CHECK_PTR(q.A);
-    LDC_CHECK_PTR(q.W);
-    LDC_CHECK_PTR(q.C);
-    const ldc_gemm_desc& d = q.d;
-    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch <= 0) return LDC_ERR_ARG;
-    LDC_CHECK_ALIGN16(q.A);
-    LDC_CHECK_ALIGN16(q.W);
-    if ((d.K & 3) || (d.lda & 3) || (d.a_bs & 3)) return LDC_ERR_ALIGN;
-    if (split_bf16 ? (d.K & 7) != 0 : (d.ldw & 3) != 0) return LDC_ERR_ALIGN;
-    if (d.act < LDC_ACT_NONE || d.act > LDC_ACT_RELU) return LDC_ERR_UNSUPPORTED;
-    if ((d.flags & ~LDC_GEMM_F32_REGSTAGE) != 0) return LDC_ERR_UNSUPPORTED;  // split activation formats: the LDS-DMA bf16x3 kernel only (K % 32 == 0)
+    const ldc_gemm_problem_plan& pp = plan.pr[i];
     DevProblem& P = a.pr[i];
     P.A = q.A;
     P.W = q.W;
@@ -498,38 +486,16 @@ static int gemm_grouped_impl(const ldc_gemm_problem* problems, int n, void* work
     P.gate = q.gate;
     P.R = q.R;
     P.C = q.C;
-    P.d = d;
-    P.tm = ldc_cdiv(d.M, BM);
-    P.tn = ldc_cdiv(d.N, BN);
-    P.kt = ldc_cdiv(d.K, BK);
-    P.unit0 = U;
-    P.tile0 = tiles;
-    const long long t = static_cast<long long>(d.batch) * P.tm * P.tn;
-    tiles += t;
-    U += t * P.kt;
+    P.d = q.d;
+    P.tm = pp.tm;
+    P.tn = pp.tn;
+    P.kt = pp.kt;
+    P.unit0 = pp.unit0;
+    P.tile0 = pp.tile0;
   }
-  if (tiles > LDC_GEMM_COUNTER_BYTES / 4 - 16) return LDC_ERR_UNSUPPORTED;  // one hand-off counter per tile (1 MiB block: 262 128 tiles)
-  const long long slot_bytes = SLOT_FLOATS * static_cast<long long>(sizeof(float));
-  long long G = 512;
-  {
-    // Balance k-steps per workgroup against slabs per split tile: time ~ (U/G) t_unit + (kt G/U) t_slab is
-    // smallest at U/G = sqrt(kt t_slab / t_unit); t_slab / t_unit ~ 2 (fp32 units) or ~ 7 (bf16x3 units).
-    const double kt_avg = static_cast<double>(U) / static_cast<double>(tiles);
-    long long umin = static_cast<long long>(sqrt(kt_avg * (split_bf16 ? 7.0 : 2.0)) + 0.5);
-    if (umin < 1) umin = 1;
-    const long long gmax = U / umin > 0 ? U / umin : 1;
-    if (gmax < G) G = gmax;
-  }
-  if (U < G) G = U;
-  if (workspace == nullptr || workspace_bytes < LDC_GEMM_COUNTER_BYTES + 2 * slot_bytes) return LDC_ERR_ARG;
-  {
-    const long long fit = (workspace_bytes - LDC_GEMM_COUNTER_BYTES) / (2 * slot_bytes);
-    if (fit < G) G = fit;  // not enough scratch for 2 slabs per workgroup: shrink the grid to what fits
-  }
-  LDC_CHECK_ALIGN16(workspace);
-  a.G = static_cast<int>(G);
-  a.U = U;
-  a.tiles = tiles;
+  a.G = plan.G;
+  a.U = plan.U;
+  a.tiles = plan.tiles;
   a.ws = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + LDC_GEMM_COUNTER_BYTES);
   a.counters = static_cast<unsigned*>(workspace);
   const size_t lds = split_bf16 ? 2 * STAGE_BYTES_B : 2 * STAGE_FLOATS * sizeof(float);
@@ -545,41 +511,6 @@ static int gemm_grouped_impl(const ldc_gemm_problem* problems, int n, void* work
   if (split_bf16) hipLaunchKernelGGL(gemm_streamk_bf16x3_kernel, dim3(a.G), dim3(256), lds, s, a);
   else hipLaunchKernelGGL(gemm_streamk_kernel, dim3(a.G), dim3(256), lds, s, a);
   return ldc_launch_status();
-}
-
-int ldc_gemm_grouped_f32_ring(const ldc_gemm_problem* problems, int n, void* workspace, long long workspace_bytes,
-                              void* stream);  // gemm_bf16x3_v3.hip, TERMS = 0
-
-extern "C" int ldc_gemm_grouped(const ldc_gemm_problem* problems, int n, void* workspace, long long workspace_bytes,
-                                void* stream) {
-  // round 3: the LDS-DMA ring kernel with fp32 operand rows and the fp32 matrix instruction where the shapes allow (K % 32 == 0,
-  // contiguous weights, 16-byte rows); the register-staged stream-K kernel below otherwise
-  const int st = ldc_gemm_grouped_f32_ring(problems, n, workspace, workspace_bytes, stream);
-  if (st != LDC_ERR_UNSUPPORTED) return st;
-  return gemm_grouped_impl(problems, n, workspace, workspace_bytes, stream, false);
-}
-
-int ldc_gemm_grouped_bf16x3_v3(const ldc_gemm_problem* problems, int n, void* workspace, long long workspace_bytes,
-                               void* stream);  // gemm_bf16x3_v3.hip
-
-extern "C" int ldc_gemm_grouped_bf16x3(const ldc_gemm_problem* problems, int n, void* workspace,
-                                       long long workspace_bytes, void* stream) {
-  // Pre-split activations (LDC_GEMM_A_SPLIT) and K % 32 == 0 - every launch of the models: the 16x16x32 ring kernel
-  // (gemm_bf16x3_v3.hip); anything else (fp32 activations, K % 32 != 0): the register-staged kernel below, which splits in its loop.
-  // A/B build only: LDC_BF16X3_KERNEL=regstage forces the register-staged kernel.
-  int force = 0;
-#ifdef LDC_AB_BUILD
-  static const int force_env = [] {
-    const char* e = getenv("LDC_BF16X3_KERNEL");
-    return (e != nullptr && strcmp(e, "regstage") == 0) ? 1 : 0;
-  }();
-  force = force_env;
-#endif
-  if (force == 0) {
-    const int st = ldc_gemm_grouped_bf16x3_v3(problems, n, workspace, workspace_bytes, stream);
-    if (st != LDC_ERR_UNSUPPORTED) return st;
-  }
-  return gemm_grouped_impl(problems, n, workspace, workspace_bytes, stream, true);
 }
 
 namespace {

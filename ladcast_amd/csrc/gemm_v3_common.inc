@@ -25,7 +25,7 @@ struct DevProblem {
   float* C;
   ldc_gemm_desc d;
   int tm, tn, kt;
-  int rm;       // tile order: super-rows of rm row tiles, inside a super-row column panel by column panel (launch_v3)
+  int rm;       // tile order: super-rows of rm row tiles, inside a super-row column panel by column panel (gemm_plan.hip)
   long long unit0;
   long long tile0;
   int vec4;     // epilogue may use 16-byte accesses

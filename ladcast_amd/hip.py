@@ -23,6 +23,7 @@ ACT_IN_TIMESTEP_SINCOS = 16  # act_in of the small linears: x = one timestep per
 GEMM_A_SPLIT, GEMM_C_SPLIT, GEMM_BF16_1TERM = 1, 2, 4
 GEMM_F32_REGSTAGE = 8  # exact-fp32 problems: stay on the register-staged stream-K kernel (include/ladcast_hip.h)
 ATTN_OUT_SPLIT, ATTN_BF16_1TERM, ATTN_OUT_BF16 = 1, 2, 4
+ERR_UNSUPPORTED = -3  # LDC_ERR_UNSUPPORTED
 ABI_VERSION = 5  # LDC_ABI_VERSION of include/ladcast_hip.h this binding was written against
 FMT_F32, FMT_SPLIT, FMT_BF16 = 0, 1, 2  # activation formats of the producers' `out_split` arguments (True == FMT_SPLIT)
 
@@ -41,6 +42,15 @@ class GemmProblem(Structure):
 
 
 MAX_GROUPED = 4
+GEMM_KERNEL_RING, GEMM_KERNEL_REGSTAGE = 0, 1  # LDC_GEMM_KERNEL_*
+
+
+class GemmPlan(Structure):  # ldc_gemm_plan: what a grouped GEMM call would run (per launch: tile_rows .. units_rem; per problem: the rest)
+    _fields_ = [("kernel", c_int), ("terms", c_int), ("launches", c_int), ("reserved", c_int),
+                ("tile_rows", c_int * MAX_GROUPED), ("workgroups", c_int * MAX_GROUPED), ("units", c_longlong * MAX_GROUPED),
+                ("tiles", c_longlong * MAX_GROUPED), ("units_per_group", c_int * MAX_GROUPED), ("units_rem", c_int * MAX_GROUPED),
+                ("tile_rows_m", c_int * MAX_GROUPED), ("tile_cols_n", c_int * MAX_GROUPED), ("k_steps", c_int * MAX_GROUPED),
+                ("super_row", c_int * MAX_GROUPED)]
 
 
 class QkvEpilogue(Structure):  # ldc_qkv_epilogue
@@ -109,6 +119,8 @@ def _load():
         "ldc_sizeof_qkv_epilogue": (I, []),
         "ldc_gemm_grouped_bf16x3_qkv": (I, [POINTER(GemmProblem), POINTER(QkvEpilogue), I, P, L, P]),
         "ldc_gemm_grouped_qkv_f32": (I, [POINTER(GemmProblem), POINTER(QkvEpilogue), I, P, L, P]),
+        "ldc_sizeof_gemm_plan": (I, []),
+        "ldc_gemm_grouped_plan": (I, [POINTER(GemmProblem), POINTER(QkvEpilogue), I, I, L, POINTER(GemmPlan)]),
         "ldc_attn_qkv_prepare_split": (I, [P, P, P, I, I, I, I, L, I, P, P, P, P, P, P, P, P, F, P]),
         "ldc_attn_fwd_split_workspace_bytes": (L, [I, I, I]),
         "ldc_attn_fwd_split_workspace_max_bytes": (L, []),
@@ -222,6 +234,8 @@ def _load():
         raise RuntimeError("ldc_gemm_desc / ldc_gemm_problem layout mismatch between header and binding")
     if lib.ldc_sizeof_qkv_epilogue() != ctypes.sizeof(QkvEpilogue):
         raise RuntimeError("ldc_qkv_epilogue layout mismatch between header and binding")
+    if lib.ldc_sizeof_gemm_plan() != ctypes.sizeof(GemmPlan):
+        raise RuntimeError("ldc_gemm_plan layout mismatch between header and binding")
     if lib.ldc_sizeof_products_desc() != ctypes.sizeof(ProductsDesc):
         raise RuntimeError("ldc_products_desc layout mismatch between header and binding")
     if lib.ldc_sizeof_events_desc() != ctypes.sizeof(EventsDesc):
@@ -329,6 +343,38 @@ def gemm_grouped(problems, split_bf16=False):
     ws = _grouped_workspace(problems[0][1][2].device)
     fn = lib.ldc_gemm_grouped_bf16x3 if split_bf16 else lib.ldc_gemm_grouped
     _check(fn(arr, n, c_void_p(ws.data_ptr()), ws.numel() * 4, _stream()), "ldc_gemm_grouped" + ("_bf16x3" if split_bf16 else ""))
+
+
+def _gemm_plan(problems, epilogues, split_bf16):
+    n = len(problems)
+    if not 1 <= n <= MAX_GROUPED or (epilogues is not None and len(epilogues) != n):
+        raise ValueError(f"gemm_plan takes 1..{MAX_GROUPED} problems and, with epilogues, one (or None) per problem")
+    arr = (GemmProblem * n)(*[p[0] for p in problems])
+    epi = None if epilogues is None else (QkvEpilogue * n)(*[(e[0] if e is not None else QkvEpilogue()) for e in epilogues])
+    plan = GemmPlan()
+    return lib.ldc_gemm_grouped_plan(arr, epi, n, int(bool(split_bf16)), lib.ldc_gemm_grouped_workspace_bytes(), ctypes.byref(plan)), plan
+
+
+def gemm_plan(problems, epilogues=None, split_bf16=False):
+    """What `gemm_grouped(problems, split_bf16)` - with `epilogues`: `gemm_grouped_qkv_f32` | `gemm_grouped_qkv` - would run with this
+    binding's workspace, as a `GemmPlan` (ldc_gemm_grouped_plan): kernel, tile height, launches, each launch's cut.  Launches nothing and
+    reads no buffer (CPU only: only the addresses' alignment matters); raises with the status the launch would fail with."""
+    st, plan = _gemm_plan(problems, epilogues, split_bf16)
+    _check(st, "ldc_gemm_grouped_plan")
+    return plan
+
+
+def gemm_kernel_name(problems, epilogues=None, split_bf16=False):
+    """the kernel instance that serves the call, as a profiler prints it (of a group launched problem by problem: the first launch's).
+    Where the fused-QKV launch is not served (LDC_ERR_UNSUPPORTED: nothing is launched, the callers run the plain grouped GEMM
+    instead) the plain GEMM's."""
+    st, plan = _gemm_plan(problems, epilogues, split_bf16)
+    if st == ERR_UNSUPPORTED and epilogues is not None:
+        st, plan = _gemm_plan(problems, None, split_bf16)
+    _check(st, "ldc_gemm_grouped_plan")
+    if plan.kernel == GEMM_KERNEL_RING:
+        return f"gemm_bf16x3_v3_kernel<{plan.tile_rows[0]}, {plan.terms}, false>"
+    return "gemm_streamk_bf16x3_kernel" if split_bf16 else "gemm_streamk_kernel"
 
 
 def gemm_sk(A, W, C, split_bf16=False, **kw):
@@ -714,7 +760,6 @@ def qkv_epilogue(wq=None, wk=None, rope=None, *, eps=1e-7, heads, rope_row0=0, q
     return QkvEpilogue(pv(wq), pv(wk), pv(rope), None, eps, qscale, heads, rope_row0), (wq, wk, rope)
 
 
-ERR_UNSUPPORTED = -3  # LDC_ERR_UNSUPPORTED
 _DEFAULT_QSCALE = ctypes.c_float(0.08838834764831845 * 1.4426950408889634).value  # log2(e) / sqrt(128) as the library rounds it
 
 

@@ -8,7 +8,7 @@ the arithmetic below.  Nothing here is fitted to what a kernel returns.
 
 GEMM  C = epilogue(A . W^T)
   exact fp32 ("f32"): terms a_k w_k.  The fp32 MFMA adds one product per step to the accumulator: K roundings.  A tile whose k range is
-    cut is summed from its pieces (launch_v3 cuts a tile into at most 8 aligned pieces, an unaligned range adds one): + 9.  Bias: + 1.
+    cut is summed from its pieces (the planner, csrc/gemm_plan.hip, cuts a tile into at most 8 aligned pieces, an unaligned range adds one): + 9.  Bias: + 1.
     n = K + 10 on S = sum_k |a w| + |bias|.
   "bf16x3": the mode's own definition on the split operands, ah.wh + ah.wl + al.wh (hi = bf16(x), lo = bf16(x - hi)).  A product of two
     bf16 values has 16 significant bits and is exact in fp32, so only the accumulation rounds: n = 3 K + 10 on the sum of the three
@@ -220,23 +220,22 @@ def tile_gemm_shapes(K=None):
 
 def sweep_K(mode, k32):
     """K of a sweep problem of k32 k-steps; capped at 768 (the single-term mode's 64-wide k-step then gives the single-tile problem 12
-    k-steps, which launch_v3 leaves whole: that mode's pieces come from the 3 x 3 problem and the group)"""
+    k-steps, which the planner leaves whole: that mode's pieces come from the 3 x 3 problem and the group)"""
     return min(k32 * KSTEP[mode], 768)
 
 
 # cut sweep: (name, [(M, N, K32, batch)])  K32: the depth in 32-wide k-steps (the single-term mode runs twice the K for the same k-steps,
-# capped by sweep_K).  What the dispatchers do with each, per kernel (gemm_bf16x3_v3.hip: launch_v3 / gemm_v3_dispatch; gemm_streamk.hip):
+# capped by sweep_K).  What the planner (csrc/gemm_plan.hip) does with each on the ring kernel is SWEEP_CUTS below, which
+# test_streamk_cut_sweep asserts on `hip.gemm_plan` of the very problems it launches; why, per entry:
 SWEEP_PROBLEMS = {
     "3x3 tiles, 9 k-steps": [(300, 260, 9, 1)],
-    # one tile, 24 k-steps: the FEW-TILES rule of launch_v3 (`few`: best < 160 and a split factor s with kt % s == 0, kt / s >= 8,
-    # tiles * s <= 256) cuts it into 3 aligned pieces of 8 k-steps on the exact-fp32 and bf16x3 ring kernels; the register-staged kernels'
-    # U / sqrt(c kt) rule gives 3 ranges too.  NOT in the single-term mode: sweep_K caps it at 12 k-steps there, which no rule cuts
-    # (G = 1 for every g: that mode's nine entries of this problem are one launch, repeated).
+    # one tile, 24 k-steps: the few-tiles branch cuts it into 3 aligned pieces of 8 k-steps on the exact-fp32 and bf16x3 ring kernels; the
+    # register-staged kernels' U / sqrt(c kt) rule gives 3 ranges too.  NOT in the single-term mode: sweep_K caps it at 12 k-steps there,
+    # which no rule cuts (G = 1 for every g: that mode's nine entries of this problem are one launch, repeated).
     "single tile, 24 k-steps": [(128, 128, 24, 1)],
     # unequal depths: the exact-fp32 ring and the register-staged kernels launch it as ONE group (unaligned ranges that cross the problem
-    # boundary).  The split ring modes (bf16x3 with split A, single-term) never do: without a common depth launch_v3 finds no aligned cut
-    # (best = few = 0), returns LDC_SPLIT_GROUP and gemm_v3_dispatch launches the problems one by one - in those modes this entry sweeps two
-    # single launches.
+    # boundary).  The split ring modes (bf16x3 with split A, single-term) never do: without a common depth there is no aligned cut and the
+    # planner gives each problem a launch of its own - in those modes this entry sweeps two single launches.
     "two problems, 9 and 2 k-steps": [(300, 260, 9, 1), (129, 136, 2, 2)],
     # equal depth 16 (9 + 8 = 17 tiles): the few-tiles rule cuts at s = 2 (34 aligned ranges) and keeps the group whole on the exact-fp32 and
     # the bf16x3 ring kernel; smaller g: unaligned ranges across the problem boundary.  Single-term mode: capped at 12 k-steps, no s with
@@ -246,6 +245,14 @@ SWEEP_PROBLEMS = {
     # workspace then cuts U = 320 units into g ranges that cross tiles, batches and the problem boundary (unit0 / tile0 of the second
     # problem, urem in either)
     "two problems, 2 k-steps each, 160 tiles": [(1279, 1020, 2, 1), (639, 1020, 2, 2)],
+}
+# workgroups of each launch the planner makes of the set with the full workspace, per arithmetic of the ring kernel
+SWEEP_CUTS = {
+    "3x3 tiles, 9 k-steps": {"f32": [10], "bf16x3": [10], "bf16": [10]},
+    "single tile, 24 k-steps": {"f32": [3], "bf16x3": [3], "bf16": [1]},
+    "two problems, 9 and 2 k-steps": {"f32": [13], "bf16x3": [10, 4], "bf16": [10, 4]},
+    "two problems, 16 k-steps each": {"f32": [34], "bf16x3": [34], "bf16": [10, 9]},
+    "two problems, 2 k-steps each, 160 tiles": {"f32": [160], "bf16x3": [160], "bf16": [160]},
 }
 SWEEP_G = (1, 2, 3, 4, 5, 7, 10, 13, 20, 32, 40, 160)  # (the register-staged kernel picks 32 for the unequal group, every kernel 160 for the last)
 

@@ -30,7 +30,7 @@ from tests.synth import rel_l2  # noqa: E402
 # 4x - 30x below the split-bf16 conv of the same data.
 FP32_GRADE = 6.0  # rel-L2 ceiling: this many times the CPU fp32 conv's own rel-L2 against float64
 ELEM_GRADE = 16.0  # element-wise ceiling: this many times the CPU fp32 conv's largest |err| / (|x| (*) |w| + |b| + |R|)
-BM, BN = 128, 128  # the ring kernel's exact-fp32 tile (gemm_bf16x3_v3.hip: launch_v3<128, 0, true>)
+BM, BN = 128, 128  # the ring kernel's exact-fp32 tile (gemm_bf16x3_v3.hip: gemm_bf16x3_v3_kernel<128, 0, true>)
 
 # (id, B, H, W, ci (the weight's input channels), cout, ksize, act, bias, resid, ldx (None: ceil4(ci)), ldy (None: cout))
 CASES = [
@@ -52,7 +52,7 @@ CASES = [
 
 
 def _tile_order(M, N, ldx):
-    """(row tiles, super-row height rm) of the conv launch, as launch_v3 chooses them (gemm_bf16x3_v3.hip)"""
+    """(row tiles, super-row height rm) of the conv launch, as the planner chooses them (csrc/gemm_plan.hip)"""
     tm, tn = -(-M // BM), -(-N // BN)
     rm = tm
     if M * ldx * 4.0 >= 48e6:

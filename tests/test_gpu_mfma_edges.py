@@ -5,8 +5,8 @@ Every operand and output is a `redzone.guarded` buffer: inputs with poisoned pad
 poisoned batch gaps, outputs UNWRITTEN, `assert_untouched` on every one after the launch - workspaces included.  A read past an extent pulls
 a NaN into the output, where the finite-ness check finds it; every element is then held to the DERIVED bound of tests/mfma_edge_refs.py
 against float64 (tests/test_mfma_edge_bounds_cpu.py judges those bounds).  The cut sweep calls the grouped entry points with a workspace
-that only fits g unit ranges, which `launch_v3` / the register-staged dispatcher document they shrink to: every cut from one range up
-to the dispatcher's own choice, without an environment variable.  The attentions run their small one-unit-per-workgroup grids over the
+that only fits g unit ranges, which the planner (csrc/gemm_plan.hip) documents it shrinks the grid to: every cut from one range up
+to the planner's own choice, without an environment variable; what that choice is, per problem set and path, is asserted through `hip.gemm_plan`.  The attentions run their small one-unit-per-workgroup grids over the
 S / Sq / bias table and, at one 260-unit shape, the other schedules: the exact-fp32 kernel's 4-wave form and balanced cut, the split
 kernel's persistent form with its key-sliced tail and merge launch - each shown to have run by what it leaves in its workspace.
 
@@ -117,6 +117,7 @@ PATHS = {
     "bf16 single term": ("bf16", FMT_BF16, 1 | 4, True, True),
     "bf16 single term, bf16 C": ("bf16", FMT_BF16, 1 | 2 | 4, True, True),
 }
+REGSTAGE_PATHS = ("f32 register-staged", "bf16x3, fp32 A")  # what `hip.gemm_plan` must say of every launch on these paths, and of no other
 TILE_PATH = "f32 tile-per-workgroup"  # ldc_gemm_bias_act: its own entry point, not a path of the grouped ones
 TILE_PATHS = {TILE_PATH: ("f32", FMT_F32, 0, False, True)}
 
@@ -186,11 +187,16 @@ class Gemm:
         return finite(p[..., self.col0:], what)
 
 
-def _run_gemm_case(hip, path, M, N, K, batch, epi, cached=True):
+def _run_gemm_case(hip, path, M, N, K, batch, epi, cached=True, tile=None):
+    """tile: the (tile rows, tiles) the planner must give the very problem that is launched"""
     mode = PATHS[path][0]
     what = f"gemm[{path}] {M} x {N} x {K}, batch {batch}, epilogue {epi}"
     inputs = R.gemm_inputs if cached else R.gemm_inputs.__wrapped__
     g = Gemm(hip, path, M, N, K, batch, epi, inputs=inputs)
+    plan = hip.gemm_plan([g.problem(hip)], split_bf16=g.split_entry)
+    assert (plan.kernel == hip.GEMM_KERNEL_REGSTAGE) == (path in REGSTAGE_PATHS) and plan.launches == 1, what
+    if tile is not None:
+        assert (plan.tile_rows[0], plan.tiles[0]) == tile, what
     hip.gemm_grouped([g.problem(hip)], split_bf16=g.split_entry)
     got = g.result(what)
     if g.c_fmt:  # operand rows out = the split of the fp32 rows the same launch shape writes, bit for bit
@@ -217,12 +223,27 @@ def test_gemm_edges(hip, path):
 
 
 def test_gemm_256_row_tile(hip):
-    """tiles256 = 20 x 21 = 420 >= 400: gemm_v3_dispatch takes the 256-row tile (two 16-row tiles per wave); 5000 = 19 x 256 + 136 rows,
-    2570 = 20 x 128 + 10 columns"""
+    """the planner takes the 256-row tile (two 16-row tiles per wave) - asserted on its plan of this launch: 20 x 21 = 420 of them;
+    5000 = 19 x 256 + 136 rows, 2570 = 20 x 128 + 10 columns"""
     M, N, K = 5000, 2570, 64
-    assert -(-M // 256) * -(-N // 128) >= 400
-    r = _run_gemm_case(hip, "bf16x3, split A", M, N, K, 1, 0, cached=False)  # (its 200 MB of float64 reference are not kept)
+    r = _run_gemm_case(hip, "bf16x3, split A", M, N, K, 1, 0, cached=False, tile=(256, 420))  # (its 200 MB of float64 reference are not kept)
     print(f"256-row tile: worst err / bound {r:.3f}")
+
+
+def test_gemm_group_launched_problem_by_problem(hip):
+    """240 + 64 = 304 tiles of 8 k-steps: no k-aligned cut reaches 160 workgroups (every aligned grid is a multiple of 19), so the split
+    mode's planner gives each problem a launch of its own - 240 whole tiles, then 64"""
+    path, mode = "bf16x3, split A", "bf16x3"
+    gemms = [Gemm(hip, path, M, 2048, 256, 1, i, inputs=R.gemm_inputs.__wrapped__) for i, M in enumerate((1920, 512))]
+    probs = [g.problem(hip) for g in gemms]
+    plan = hip.gemm_plan(probs, split_bf16=True)
+    assert plan.launches == 2
+    assert (plan.kernel, list(plan.tile_rows[:2]), list(plan.workgroups[:2]), list(plan.tiles[:2])) == (hip.GEMM_KERNEL_RING, [128, 128], [240, 64], [240, 64])
+    hip.gemm_grouped(probs, split_bf16=True)
+    for i, g in enumerate(gemms):
+        what = f"split group, problem {i}"
+        want, bound = R.gemm_ref(mode=mode, **g.kw)
+        note("gemm", path, ("split group", i), assert_elementwise(g.result(what), want, bound, what))
 
 
 # ---- the stream-K cut sweep -------------------------------------------------------------------------------------------------------
@@ -253,6 +274,11 @@ def test_streamk_cut_sweep(hip, path, name):
     gemms = [Gemm(hip, path, M, N, R.sweep_K(mode, k32), batch, i) for i, (M, N, k32, batch) in enumerate(R.SWEEP_PROBLEMS[name])]
     refs = [R.gemm_case_ref(g.M, g.N, g.K, g.batch, i, mode) for i, g in enumerate(gemms)]
     split_entry = gemms[0].split_entry
+    plan = hip.gemm_plan([g.problem(hip) for g in gemms], split_bf16=split_entry)
+    if path in REGSTAGE_PATHS:
+        assert (plan.kernel, plan.launches) == (hip.GEMM_KERNEL_REGSTAGE, 1)
+    else:  # ring kernel: (launches, workgroups of each) as written beside R.SWEEP_PROBLEMS
+        assert plan.kernel == hip.GEMM_KERNEL_RING and list(plan.workgroups[: plan.launches]) == R.SWEEP_CUTS[name][mode], (path, name)
     for g_ranges in R.SWEEP_G:
         ws, nbytes = _workspace(hip, g_ranges)
         outs = []
