@@ -1,4 +1,9 @@
-"""ctypes binding of the C ABI in ``include/ladcast_hip.h``.
+"""ctypes binding of the C ABI in ``include/ladcast_hip.h``, generated from that header.
+
+``ladcast_amd.abi`` reads the header at import: its prototypes become ``SIGNATURES`` (restype and argtypes of every entry point) and
+its ``ldc_*`` structs the ``ctypes.Structure`` classes named below, so a new entry point needs its prototype in the header and a
+wrapper here, nothing else.  The constants stay literals, since call sites read them by name; tests/test_abi_cpu.py holds them to
+the header.
 
 PyTorch is plumbing here: it owns device memory and the HIP stream.  Every wrapper takes
 torch CUDA(=HIP) tensors, passes raw device pointers + sizes + the current stream to the
@@ -10,9 +15,11 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_void_p
+from ctypes import c_int, c_void_p
 
 import torch
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LDC_LIB_PATH: diagnostic builds only (e.g. the in-kernel stamp build made by `make stamps`)
@@ -26,76 +33,26 @@ ATTN_OUT_SPLIT, ATTN_BF16_1TERM, ATTN_OUT_BF16 = 1, 2, 4
 ERR_UNSUPPORTED = -3  # LDC_ERR_UNSUPPORTED
 ABI_VERSION = 5  # LDC_ABI_VERSION of include/ladcast_hip.h this binding was written against
 FMT_F32, FMT_SPLIT, FMT_BF16 = 0, 1, 2  # activation formats of the producers' `out_split` arguments (True == FMT_SPLIT)
-
-
-class GemmDesc(Structure):
-    _fields_ = [
-        ("M", c_int), ("N", c_int), ("K", c_int), ("batch", c_int),
-        ("lda", c_int), ("ldw", c_int), ("ldc", c_int), ("ldr", c_int),
-        ("a_bs", c_longlong), ("c_bs", c_longlong), ("r_bs", c_longlong),
-        ("gate_bs", c_int), ("act", c_int), ("flags", c_int), ("reserved", c_int),
-    ]
-
-
-class GemmProblem(Structure):
-    _fields_ = [("A", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("gate", c_void_p), ("R", c_void_p), ("C", c_void_p), ("d", GemmDesc)]
-
-
 MAX_GROUPED = 4
 GEMM_KERNEL_RING, GEMM_KERNEL_REGSTAGE = 0, 1  # LDC_GEMM_KERNEL_*
-
-
-class GemmPlan(Structure):  # ldc_gemm_plan: what a grouped GEMM call would run (per launch: tile_rows .. units_rem; per problem: the rest)
-    _fields_ = [("kernel", c_int), ("terms", c_int), ("launches", c_int), ("reserved", c_int),
-                ("tile_rows", c_int * MAX_GROUPED), ("workgroups", c_int * MAX_GROUPED), ("units", c_longlong * MAX_GROUPED),
-                ("tiles", c_longlong * MAX_GROUPED), ("units_per_group", c_int * MAX_GROUPED), ("units_rem", c_int * MAX_GROUPED),
-                ("tile_rows_m", c_int * MAX_GROUPED), ("tile_cols_n", c_int * MAX_GROUPED), ("k_steps", c_int * MAX_GROUPED),
-                ("super_row", c_int * MAX_GROUPED)]
-
-
-class QkvEpilogue(Structure):  # ldc_qkv_epilogue
-    _fields_ = [("wq", c_void_p), ("wk", c_void_p), ("rope", c_void_p), ("reserved", c_void_p), ("eps", c_float), ("qscale", c_float),
-                ("heads", c_int), ("rope_row0", c_int)]
-
-
-class LinearSmallProblem(Structure):  # ldc_linear_small_problem
-    _fields_ = [("x", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("add", c_void_p), ("y", c_void_p), ("x_rows", c_int), ("add_rows", c_int),
-                ("rows", c_int), ("N", c_int), ("K", c_int), ("act_in", c_int), ("act_out", c_int), ("reserved", c_int)]
-
-
 PRODUCTS_MAX_QUANTILES, PRODUCTS_MAX_THRESHOLDS, PRODUCTS_MAX_MEMBERS, PRODUCTS_MAX_SORT_MEMBERS = 16, 8, 1024, 64  # LDC_PRODUCTS_MAX_*
-
-
-class ProductsDesc(Structure):  # ldc_products_desc
-    _fields_ = [("n_quant", c_int), ("n_thr", c_int), ("q_lo", c_int * PRODUCTS_MAX_QUANTILES), ("q_t", c_float * PRODUCTS_MAX_QUANTILES),
-                ("thr_dir", c_int * PRODUCTS_MAX_THRESHOLDS)]
-
-
 EVENTS_MAX, EVENTS_MAX_MEMBERS = 32, 1024  # LDC_EVENTS_MAX, the largest ensemble of ldc_rollout_events
-
-
 FSS_SCALES_MAX, FSS_SUMS = 16, 6  # LDC_FSS_SCALES_MAX, the sums per (event, radius, lead time) of ldc_rollout_fss
-
-
 DERIVE_MAX_FIELDS = 16  # LDC_DERIVE_MAX_FIELDS
 DERIVE_SPEED, DERIVE_DIFF, DERIVE_SHEAR = 0, 1, 2  # LDC_DERIVE_*
 DERIVE_INPUTS = {DERIVE_SPEED: 2, DERIVE_DIFF: 2, DERIVE_SHEAR: 4}  # source channels per kind
-
-
-class DeriveDesc(Structure):  # ldc_derive_desc
-    _fields_ = [("kind", c_int), ("ch", c_int * 4)]
-
-
 SPHERE_VORTICITY, SPHERE_DIVERGENCE = 0, 1  # LDC_SPHERE_*: fields of a wind (u, v) that need horizontal derivatives
 
-
-class SphereDesc(Structure):  # ldc_sphere_desc
-    _fields_ = [("kind", c_int), ("ch", c_int * 2)]
-
-
-class EventsDesc(Structure):  # ldc_events_desc
-    _fields_ = [("n_events", c_int), ("channel", c_int * EVENTS_MAX), ("dir", c_int * EVENTS_MAX), ("anomaly", c_int * EVENTS_MAX),
-                ("thr", c_float * EVENTS_MAX)]
+# the header's structs: field names, order and types are the header's (a pointer field is a c_void_p)
+GemmDesc = abi.STRUCTS["ldc_gemm_desc"]
+GemmProblem = abi.STRUCTS["ldc_gemm_problem"]
+GemmPlan = abi.STRUCTS["ldc_gemm_plan"]  # what a grouped GEMM call would run (per launch: tile_rows .. units_rem; per problem: the rest)
+QkvEpilogue = abi.STRUCTS["ldc_qkv_epilogue"]
+LinearSmallProblem = abi.STRUCTS["ldc_linear_small_problem"]
+ProductsDesc = abi.STRUCTS["ldc_products_desc"]
+DeriveDesc = abi.STRUCTS["ldc_derive_desc"]
+SphereDesc = abi.STRUCTS["ldc_sphere_desc"]
+EventsDesc = abi.STRUCTS["ldc_events_desc"]
 
 
 def _load():
@@ -105,149 +62,20 @@ def _load():
             "(or `make -C ladcast_amd/csrc`).  ladcast_amd has no CPU fallback."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    P, I, L, F, D = c_void_p, c_int, c_longlong, c_float, c_double
-    sig = {
-        "ldc_abi_version": (I, []),
-        "ldc_build_arch": (c_char_p, []),
-        "ldc_sizeof_gemm_desc": (I, []),
-        "ldc_gemm_bias_act": (I, [P, P, P, P, P, P, POINTER(GemmDesc), P]),
-        "ldc_sizeof_gemm_problem": (I, []),
-        "ldc_gemm_grouped_workspace_bytes": (L, []),
-        "ldc_gemm_grouped_workspace_init": (I, [P, L, P]),
-        "ldc_gemm_grouped": (I, [POINTER(GemmProblem), I, P, L, P]),
-        "ldc_gemm_grouped_bf16x3": (I, [POINTER(GemmProblem), I, P, L, P]),
-        "ldc_sizeof_qkv_epilogue": (I, []),
-        "ldc_gemm_grouped_bf16x3_qkv": (I, [POINTER(GemmProblem), POINTER(QkvEpilogue), I, P, L, P]),
-        "ldc_gemm_grouped_qkv_f32": (I, [POINTER(GemmProblem), POINTER(QkvEpilogue), I, P, L, P]),
-        "ldc_sizeof_gemm_plan": (I, []),
-        "ldc_gemm_grouped_plan": (I, [POINTER(GemmProblem), POINTER(QkvEpilogue), I, I, L, POINTER(GemmPlan)]),
-        "ldc_attn_qkv_prepare_split": (I, [P, P, P, I, I, I, I, L, I, P, P, P, P, P, P, P, P, F, P]),
-        "ldc_attn_fwd_split_workspace_bytes": (L, [I, I, I]),
-        "ldc_attn_fwd_split_workspace_max_bytes": (L, []),
-        "ldc_attn_fwd_split": (I, [P, P, P, P, I, I, I, I, L, I, L, P, I, P, L, P]),
-        "ldc_attn_fwd_split_qrows_workspace_bytes": (L, [I, I, I, I]),
-        "ldc_attn_fwd_split_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, I, P, L, P]),
-        "ldc_pack_weight_bf16x2": (I, [P, P, I, I, I, P]),
-        "ldc_pack_weight_bf16": (I, [P, P, I, I, I, P]),
-        "ldc_linear_small": (I, [P, I, P, P, P, I, P, I, I, I, I, I, P]),
-        "ldc_linear_small_grouped": (I, [POINTER(LinearSmallProblem), I, P]),
-        "ldc_linear_small_mod": (I, [P, I, P, P, P, I, P, I, P, I, I, I, I, I, P]),
-        "ldc_gate_residual_layernorm": (I, [P, P, P, P, I, I, I, I, L, I, L, I, I, L, P, P, F, I, P]),
-        "ldc_attn_fwd": (I, [P, P, P, P, I, I, I, I, L, I, L, P, P]),
-        "ldc_attn_fwd_ws": (I, [P, P, P, P, I, I, I, I, L, I, L, P, P, L, P]),
-        "ldc_attn_fwd_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P]),
-        "ldc_attn_fwd_ws_qrows": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P, L, P]),
-        "ldc_attn_fwd_ws_qrows_thr": (I, [P, P, P, P, I, I, I, I, I, L, I, L, P, P, L, F, P]),
-        "ldc_attn_fwd_workspace_bytes": (L, []),
-        "ldc_qk_rmsnorm_rope": (I, [P, P, I, I, I, I, I, L, P, P, F, P, P, P]),
-        "ldc_sphere_conv_nhwc_split": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, L, P]),
-        "ldc_sphere_conv_plan": (I, [I, I, I, I, I, I, I, P, P]),
-        "ldc_rmsnorm_rows_split": (I, [P, P, P, P, P, P, L, I, I, I, I, I, I, F, I, P]),
-        "ldc_pixel_unshuffle_shortcut_split": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
-        "ldc_pixel_shuffle_shortcut_split": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
-        "ldc_pixel_shuffle_to_chan": (I, [P, P, I, I, I, I, I, P]),
-        "ldc_split_rows": (I, [P, P, L, I, I, I, I, P]),
-        "ldc_upsample_nearest2x_rows": (I, [P, P, P, I, I, I, I, I, I, I, I, P]),
-        "ldc_sphere_dwconv_nhwc_fmt": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
-        "ldc_relu_linear_attn_nhwc_fmt": (I, [P, P, I, I, I, I, I, F, I, P, L, P]),
-        "ldc_ensemble_scores_workspace_bytes": (L, [I, I, I]),
-        "ldc_ensemble_scores": (I, [P, L, L, P, L, P, L, P, I, I, I, I, I, P, P, P, P, L, P]),
-        "ldc_rollout_scores_workspace_bytes": (L, [I, I, I, I]),
-        "ldc_rollout_scores": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, I, P, I, I, P, L, P]),
-        "ldc_validation_scores_workspace_bytes": (L, [I, I, I, I]),
-        "ldc_validation_scores": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, P, I, I, P, L, P]),
-        "ldc_rollout_reliability_workspace_bytes": (L, [I, I, I, I, I]),
-        "ldc_rollout_reliability": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, L, P]),
-        "ldc_rollout_spectrum_workspace_bytes": (L, [I, I, I, I, I]),
-        "ldc_rollout_spectrum": (I, [P, L, L, L, P, P, F, P, L, L, P, P, I, I, I, I, I, P, P, I, I, P, L, P]),
-        "ldc_sizeof_products_desc": (I, []),
-        "ldc_rollout_products": (I, [P, L, L, L, P, P, F, P, I, I, I, I, I, I, POINTER(ProductsDesc), P, P, P, P, I, I, P]),
-        "ldc_sizeof_events_desc": (I, []),
-        "ldc_rollout_events_workspace_bytes": (L, [I, I, I, I, I]),
-        "ldc_rollout_events": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, POINTER(EventsDesc), P, P, P, I, I, P, L, P]),
-        "ldc_rollout_fss_workspace_bytes": (L, [I, I, I, I, I, I]),
-        "ldc_rollout_fss": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, I, I, I, I, I, POINTER(EventsDesc), POINTER(c_int), I, P, P, I, I, P, L, P]),
-        "ldc_rollout_regional_workspace_bytes": (L, [I, I, I, I, I, I]),
-        "ldc_rollout_regional": (I, [P, L, L, L, P, P, F, P, L, L, P, P, L, L, P, P, P, I, I, I, I, I, I, P, P, I, I, P, L, P]),
-        "ldc_rollout_energy_workspace_bytes": (L, [I, I, I, I, I, I]),
-        "ldc_rollout_energy": (I, [P, L, L, L, P, P, F, P, L, L, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, L, P]),
-        "ldc_layernorm_mod": (I, [P, P, I, I, I, I, L, I, L, P, P, I, I, F, I, P]),
-        "ldc_layernorm_mod2": (I, [P, P, I, I, I, I, L, I, L, P, P, I, P, P, I, I, F, I, P]),
-        "ldc_mean_rows": (I, [P, P, I, I, I, I, L, P]),
-        "ldc_mean_rows_split": (I, [P, P, P, I, I, I, I, L, I, L, I, P]),
-        "ldc_chan_to_token_split": (I, [P, P, I, I, I, I, I, I, P]),
-        "ldc_gate_residual": (I, [P, P, P, P, I, I, I, I, L, I, L, I, P]),
-        "ldc_chan_to_token": (I, [P, P, I, I, I, I, I, P]),
-        "ldc_token_to_chan": (I, [P, P, I, I, I, I, P]),
-        "ldc_timestep_embedding": (I, [P, P, I, P]),
-        "ldc_temb_modulate": (I, [P, P, I, I, I, P]),
-        "ldc_chan_affine": (I, [P, P, P, P, F, L, I, L, I, P]),
-        "ldc_edm_scale_f64_to_f32": (I, [P, D, P, L, P]),
-        "ldc_edm_init_state": (I, [P, D, P, L, P]),
-        "ldc_edm_euler": (I, [P, P, D, D, D, D, P, P, L, P]),
-        "ldc_edm_churn": (I, [P, P, c_double, P, L, P]),
-        "ldc_edm_heun": (I, [P, P, P, P, D, D, D, D, L, P]),
-        "ldc_f64_to_f32": (I, [P, P, L, P]),
-        "ldc_dpm_step": (I, [P, P, P, P, P, F, F, F, F, F, I, L, P]),
-        "ldc_ddim_step": (I, [P, P, P, P, P, F, F, F, F, F, F, I, I, L, P]),
-        "ldc_ddpm_step": (I, [P, P, P, P, P, F, F, F, F, F, F, I, L, P]),
-        "ldc_scale_f32": (I, [P, F, P, L, P]),
-        "ldc_axpby_f32": (I, [P, F, P, F, P, L, P]),
-        "ldc_edm_noise_inputs": (I, [P, P, P, P, P, P, I, L, P]),
-        "ldc_edm_denoise": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
-        "ldc_edm_denoise_loss": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
-        "ldc_sphere_conv_nhwc": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
-        "ldc_sphere_dwconv_nhwc": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
-        "ldc_grouped_conv1x1_nhwc": (I, [P, P, P, L, I, I, I, P]),
-        "ldc_relu_linear_attn_nhwc": (I, [P, P, I, I, I, I, I, F, P, L, P]),
-        "ldc_relu_linear_attn_workspace_bytes": (L, [I, I, I]),
-        "ldc_rmsnorm_rows": (I, [P, P, P, P, P, L, I, I, I, I, F, I, P]),
-        "ldc_pixel_unshuffle_shortcut": (I, [P, P, P, I, I, I, I, I, P]),
-        "ldc_pixel_shuffle_shortcut": (I, [P, P, P, I, I, I, I, I, P]),
-        "ldc_chan_regroup": (I, [P, P, L, I, I, P]),
-        "ldc_track_gather": (I, [P, L, L, L, I, I, L, POINTER(c_int), I, P, P, F, P, I, I, P]),
-        "ldc_sizeof_derive_desc": (I, []),
-        "ldc_derive_fields": (I, [P, L, L, L, P, P, P, F, I, I, I, L, POINTER(DeriveDesc), I, P, L, L, L, P]),
-        "ldc_sizeof_sphere_desc": (I, []),
-        "ldc_derive_sphere": (I, [P, L, L, L, P, P, P, F, I, I, I, I, I, P, D, POINTER(SphereDesc), I, P, L, L, L, P]),
-        "ldc_track_nanmean": (I, [P, L, I, L, P, P]),
-        "ldc_track_storms": (I, [P, L, L, L, L, P, P, I, P, I, P, P, I, I, POINTER(c_int), I, I, P, P, P, P]),
-        "ldc_track_local_min": (I, [P, L, P, P, I, P, I, P, P, P, I, P, P, P, P, P]),
-        "ldc_recon_preprocess": (I, [P, L, L, L, I, I, I, I, P, P, I, P, P, P]),
-        "ldc_recon_scores_workspace_bytes": (L, [I, I, I, I]),
-        "ldc_recon_scores": (I, [P, P, P, L, P, P, P, P, I, I, I, I, I, I, P, P, P, P, L, P]),
-        "ldc_field_moments_workspace_bytes": (L, [I, I, I, I]),
-        "ldc_field_moments": (I, [P, L, L, L, I, I, I, I, P, I, P, L, P]),
-        "ldc_climatology_accumulate": (I, [P, L, L, L, I, I, I, I, P, I, P, P, P]),
-        "ldc_climatology_smooth": (I, [P, P, P, I, I, I, I, L, P, P, P]),
-        "ldc_paired_bootstrap_max_replicates": (I, []),
-        "ldc_paired_bootstrap_workspace_bytes": (L, [I, I, I, I]),
-        "ldc_paired_bootstrap": (I, [P, P, L, I, I, P, I, I, I, I, P, P, P, L, P]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in abi.SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
     if lib.ldc_abi_version() != ABI_VERSION:
         raise RuntimeError("libladcast_hip.so ABI version mismatch")
-    if lib.ldc_sizeof_gemm_desc() != ctypes.sizeof(GemmDesc) or lib.ldc_sizeof_gemm_problem() != ctypes.sizeof(GemmProblem):
-        raise RuntimeError("ldc_gemm_desc / ldc_gemm_problem layout mismatch between header and binding")
-    if lib.ldc_sizeof_qkv_epilogue() != ctypes.sizeof(QkvEpilogue):
-        raise RuntimeError("ldc_qkv_epilogue layout mismatch between header and binding")
-    if lib.ldc_sizeof_gemm_plan() != ctypes.sizeof(GemmPlan):
-        raise RuntimeError("ldc_gemm_plan layout mismatch between header and binding")
-    if lib.ldc_sizeof_products_desc() != ctypes.sizeof(ProductsDesc):
-        raise RuntimeError("ldc_products_desc layout mismatch between header and binding")
-    if lib.ldc_sizeof_events_desc() != ctypes.sizeof(EventsDesc):
-        raise RuntimeError("ldc_events_desc layout mismatch between header and binding")
-    if lib.ldc_sizeof_derive_desc() != ctypes.sizeof(DeriveDesc):
-        raise RuntimeError("ldc_derive_desc layout mismatch between header and binding")
-    if lib.ldc_sizeof_sphere_desc() != ctypes.sizeof(SphereDesc):
-        raise RuntimeError("ldc_sphere_desc layout mismatch between header and binding")
-    return lib, sig
+    for name, cls in abi.STRUCTS.items():  # every struct whose size the library reports, as its compiler laid it out
+        size_of = "ldc_sizeof_" + name[len("ldc_"):]
+        if size_of in abi.SIGNATURES and getattr(lib, size_of)() != ctypes.sizeof(cls):
+            raise RuntimeError(f"{name} layout mismatch between header and binding")
+    return lib
 
 
-lib, SIGNATURES = _load()
+lib, SIGNATURES = _load(), abi.SIGNATURES
 
 
 def _check(status: int, what: str):
