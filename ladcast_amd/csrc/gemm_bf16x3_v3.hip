@@ -32,6 +32,7 @@ namespace {
 
 #include "gemm_v3_common.inc"
 #include "gemm_v3_kstep_f32.inc"
+#include "gemm_v3_kstep_f32_nocopy.inc"
 
 struct SKArgs {
   DevProblem pr[MAXP];
@@ -440,6 +441,10 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(SKArgs a) {
 #else
   constexpr bool PAIRED = TERMS == 0 && RT == 1;
 #endif
+  // the GEMM's instance of it: LDC_KSTEP_QC (gemm_v3_kstep_f32_nocopy.inc) - the same instructions with waits that redefine no fragment register.
+  // LDC_KSTEP_Q's waits do, and its loop holds compiler-made copies out of registers whose ds_read is still in flight, ahead of the wait that
+  // retires it (harmless only while enough of the wave's own MFMAs happen to sit in between).  The gathered conv keeps LDC_KSTEP_Q.
+  constexpr bool NOCOPY = PAIRED && !CONV;
 
     // prologue: k-steps k0 and k0+1 in flight, fragments of k0 (A, W column tiles 0-3) loading
 #ifdef LDC_GEMM_STAMPS_PROLOGUE
@@ -466,7 +471,9 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(SKArgs a) {
     __builtin_amdgcn_s_barrier();
     LDC_STAMP(1 + 4 * seg_)
     if (seg_ == 0) { LDC_STAMP_CLK(13) }
-    if constexpr (PAIRED) {
+    if constexpr (NOCOPY) {
+      // (its prologue reads are issued in front of each of its two loop bodies: one definition per path, nothing to merge while they are in flight)
+    } else if constexpr (PAIRED) {
       LDC_KSTEP_Q_PROLOGUE(ah0, al0)
     } else {
       LDC_RD_A(ah0, al0, a_hi, a_lo)
@@ -481,7 +488,31 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(SKArgs a) {
 
     unsigned sb = 0;  // LDS byte offset of stage kt
     int st = 0;       // stage index of k-step kt
-    if constexpr (PAIRED) {
+    if constexpr (NOCOPY) {
+      static_assert(!NOCOPY || ND == 4, "the interleaved k-step is written for the 128-row tile's 4 DMA pieces");
+      // leaving the loop: the (unused) reads of the k-step that will not run are drained before anything else can be given their registers
+#define LDC_KSTEP_QC_DRAIN(AH, AL)                                                                                                      \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(AH[0]), "v"(AL[0]), "v"(wh0), "v"(wl0), "v"(wh1), "v"(wl1), "v"(wh2), "v"(wh3));          \
+  LDC_SB;
+      if (wave_rows) {
+        LDC_KSTEP_QC_PROLOGUE(ah0, al0)
+        for (int kt = k0;;) {
+          LDC_KSTEP_QC(ah0, al0, ah1, al1, LDC_MM_ON)
+          if (++kt >= k1) { LDC_KSTEP_QC_DRAIN(ah1, al1) break; }
+          LDC_KSTEP_QC(ah1, al1, ah0, al0, LDC_MM_ON)
+          if (++kt >= k1) { LDC_KSTEP_QC_DRAIN(ah0, al0) break; }
+        }
+      } else {
+        LDC_KSTEP_QC_PROLOGUE(ah0, al0)
+        for (int kt = k0;;) {
+          LDC_KSTEP_QC(ah0, al0, ah1, al1, LDC_MM_OFF)
+          if (++kt >= k1) { LDC_KSTEP_QC_DRAIN(ah1, al1) break; }
+          LDC_KSTEP_QC(ah1, al1, ah0, al0, LDC_MM_OFF)
+          if (++kt >= k1) { LDC_KSTEP_QC_DRAIN(ah0, al0) break; }
+        }
+      }
+#undef LDC_KSTEP_QC_DRAIN
+    } else if constexpr (PAIRED) {
       static_assert(!PAIRED || ND == 4, "the interleaved k-step is written for the 128-row tile's 4 DMA pieces");
       if (wave_rows) {
         for (int kt = k0; kt < k1; ++kt) {
@@ -506,10 +537,12 @@ __global__ __launch_bounds__(512) void gemm_bf16x3_v3_kernel(SKArgs a) {
         LDC_KSTEP(ah1, al1, ah0, al0)
       }
     }
-    // drain the (unused) reads of the last k-step before their registers are reused
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wh0), "+v"(wl0), "+v"(wh1), "+v"(wl1), "+v"(wh2), "+v"(wl2), "+v"(wh3), "+v"(wl3));
+    if constexpr (!NOCOPY) {  // (the copy-free loop drains where it leaves)
+      // drain the (unused) reads of the last k-step before their registers are reused
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wh0), "+v"(wl0), "+v"(wh1), "+v"(wl1), "+v"(wh2), "+v"(wl2), "+v"(wh3), "+v"(wl3));
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) asm volatile("" : "+v"(ah0[rt]), "+v"(al0[rt]), "+v"(ah1[rt]), "+v"(al1[rt]));
+      for (int rt = 0; rt < RT; ++rt) asm volatile("" : "+v"(ah0[rt]), "+v"(al0[rt]), "+v"(ah1[rt]), "+v"(al1[rt]));
+    }
 #undef LDC_KSTEP
 #undef LDC_MM_ON
 #undef LDC_MM_OFF
@@ -662,6 +695,10 @@ int launch_v3(const ldc_gemm_problem* problems, int n, const ldc_gemm_launch_pla
 int ldc_gemm_ring_launch(const ldc_gemm_problem* problems, int n, const ldc_gemm_launch_plan& plan, int bm, int terms,
                          const ldc_conv_params* cp, void* workspace, void* stream) {
   const bool sm = bm == 128;
+#ifdef LDC_GEMM_F32_INSTANCES_ONLY  // tools/kloop_isa.py: only the two exact-fp32 instances are compiled (seconds instead of minutes; the same code for them)
+  if (terms != 0 || !sm) return LDC_ERR_UNSUPPORTED;
+  return cp == nullptr ? launch_v3<128, 0>(problems, n, plan, cp, workspace, stream) : launch_v3<128, 0, true>(problems, n, plan, cp, workspace, stream);
+#else
   if (cp == nullptr) {
     if (terms == 1)
       return sm ? launch_v3<128, 1>(problems, n, plan, cp, workspace, stream) : launch_v3<256, 1>(problems, n, plan, cp, workspace, stream);
@@ -676,6 +713,7 @@ int ldc_gemm_ring_launch(const ldc_gemm_problem* problems, int n, const ldc_gemm
   if (terms == 1)
     return sm ? launch_v3<128, 1, true>(problems, n, plan, cp, workspace, stream) : launch_v3<256, 1, true>(problems, n, plan, cp, workspace, stream);
   return sm ? launch_v3<128, 3, true>(problems, n, plan, cp, workspace, stream) : launch_v3<256, 3, true>(problems, n, plan, cp, workspace, stream);
+#endif
 }
 
 // SphereConv2d (dense, stride 1, k = 3 / 5; k = 1: pointwise conv / Linear over pixel rows) as an implicit GEMM on the pre-split kernel.
