@@ -1,4 +1,6 @@
 """The C ABI as ``include/ladcast_hip.h`` declares it, read from the header itself: constants, struct layouts and prototypes.
+``include/ladcast_hip_ext.h``, the header of the entry points added after the recorded set of the first one, is read the same way into
+``EXT_CONSTANTS`` and ``EXT_SIGNATURES``; it declares no struct, and a name it shares with the first header raises at import.
 
 ``ladcast_amd.hip`` builds its ctypes binding from this, so the header is the only place an entry point is declared.  The reader is
 strict: a type it does not know, a statement it cannot split or an array bound it cannot resolve raises at import and names the item.
@@ -9,6 +11,7 @@ import os
 import re
 
 HEADER_PATH = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "ladcast_hip.h"))
+EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ladcast_hip_ext.h")
 
 _SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double}
 _NAME = r"[A-Za-z_]\w*"
@@ -77,11 +80,22 @@ def parse(text):
     return constants, structs, signatures
 
 
-def _read():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f"{HEADER_PATH} is missing: ladcast_amd.hip derives its binding of libladcast_hip.so from this header.")
-    with open(HEADER_PATH) as f:
+def _read(path=HEADER_PATH):
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: ladcast_amd.hip derives its binding of libladcast_hip.so from this header.")
+    with open(path) as f:
         return f.read()
 
 
 CONSTANTS, STRUCTS, SIGNATURES = parse(_read())
+
+
+def _parse_ext():
+    constants, structs, signatures = parse(_read(EXT_HEADER_PATH))
+    shared = sorted((set(constants) & set(CONSTANTS)) | (set(signatures) & set(SIGNATURES)))
+    if structs or shared:
+        raise ValueError(f"{EXT_HEADER_PATH}: declares structs {sorted(structs)} / repeats {shared} of ladcast_hip.h; it takes flat arguments and new names only")
+    return constants, signatures
+
+
+EXT_CONSTANTS, EXT_SIGNATURES = _parse_ext()

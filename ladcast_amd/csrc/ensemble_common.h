@@ -1,9 +1,12 @@
-// Shared by the ensemble-statistics kernels (scoring.hip, reliability.hip, spectrum.hip, products.hip, regional.hip, energy.hip and, through
+// Shared by the ensemble-statistics kernels (scoring.hip, reliability.hip, spectrum.hip, products.hip, regional.hip, score_maps.hip, energy.hip and, through
 // events_common.h, events.hip and fss.hip): the fused inverse normalisation, the register sort with its (NP, NUSE) ladder over the ensemble
-// size, the members-in-registers ladder, and RolloutView - how the nine entry points that read a decoded rollout (ldc_rollout_scores,
-// ldc_validation_scores, ldc_rollout_reliability / _spectrum / _products / _events / _fss / _regional / _energy) address a forecast, its truth
-// and its climatology, with the one host function that checks and fills it.  ldc_ensemble_scores (one lead time, no slots) keeps its own.
+// size, the members-in-registers ladder, the point values that the regional scores and the score maps share, and RolloutView - how the
+// ten entry points that read a decoded rollout (ldc_rollout_scores, ldc_validation_scores, ldc_rollout_reliability / _spectrum / _products /
+// _events / _fss / _regional / _score_maps / _energy) address a forecast, its truth and its climatology, with the one host function that
+// checks and fills it.  ldc_ensemble_scores (one lead time, no slots) keeps its own.
 #pragma once
+#include <math.h>
+
 #include <type_traits>
 
 #include "common.h"
@@ -120,20 +123,91 @@ __device__ __forceinline__ float load_member(const float* f, int i, long long fc
   return v;
 }
 
+// The per-point values of the regional scores and the score maps (regional.hip, score_maps.hip; the formulas in regional.hip's header), every
+// one fp32 and formed in one fixed order, so that both kernels hold the same bits: mean sequential in member order, var two-pass, skill,
+// spread through the sorted members with one explicit fused multiply-add per step, the anomalies against the climatology and their three
+// products.  valid: no member and not the truth is NaN; acc_valid: valid and the climatology is not NaN.  f: member 0 of the point, tp: its
+// truth, clp: its climatology or nullptr (fta, ffa, tta are then 0 and acc_valid false).  Contraction is switched off here as in inv_norm.
+struct PointValues {
+  float e, se, var, skill, spread, fta, ffa, tta;
+  bool valid, acc_valid;
+};
+
+template <int NP, int NUSE, bool INV>
+__device__ __forceinline__ PointValues ensemble_point_values(const float* f, long long fc_ms, const InvNorm& nrm, int M, const float* tp,
+                                                             const float* clp) {
+#pragma clang fp contract(off)
+  const float Mf = static_cast<float>(M);
+  float x[NP];
+  bool nan_m = false;
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    if (i < NUSE && i < M) {
+      const float v = load_member<INV>(f, i, fc_ms, nrm);
+      x[i] = v;
+      sum += v;
+      nan_m = nan_m || (v != v);
+    } else {
+      x[i] = INFINITY;  // sorts behind every member
+    }
+  }
+  const float t = *tp;
+  float skill = 0.f;
+#pragma unroll
+  for (int i = 0; i < NUSE; ++i)
+    if (i < M) skill += fabsf(t - x[i]);
+  skill /= Mf;
+  const float mean = sum / Mf;
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < NUSE; ++i)
+    if (i < M) {
+      const float d = x[i] - mean;
+      ss += d * d;
+    }
+  float var = 0.f, spread = 0.f;
+  if (M >= 2) {
+    var = ss / (Mf - 1.0f);
+    sort_network<NP, NUSE>(x);
+    float ws = 0.f;
+#pragma unroll
+    for (int i = 0; i < NUSE; ++i)
+      if (i < M) ws = fmaf(x[i], 2.0f * static_cast<float>(i + 1) - Mf - 1.0f, ws);
+    spread = 2.0f * ws / (Mf * (Mf - 1.0f));
+  }
+  PointValues r{};
+  r.e = mean - t;
+  r.se = r.e * r.e;
+  r.var = var;
+  r.skill = skill;
+  r.spread = spread;
+  r.valid = !nan_m && t == t;
+  if (clp) {
+    const float cl = *clp;
+    const float fa = mean - cl, ta = t - cl;
+    r.fta = fa * ta;
+    r.ffa = fa * fa;
+    r.tta = ta * ta;
+    r.acc_valid = r.valid && cl == cl;
+  }
+  return r;
+}
+
 // Checks and fills the view from the leading C arguments of a rollout entry point, in ABI order, for a forecast written to columns
 // l_off .. l_off + L - 1 of L_total: LDC_OK or LDC_ERR_ARG.  Entry points without a climatology pass nullptr, 0, 0, nullptr; with_truth =
-// false (products) also waives truth, truth_slot and lat_weight.  Pointer checks and limits of its own (LDC_ERR_UNSUPPORTED) stay with each
+// false (products) also waives truth, truth_slot and lat_weight; with_weight = false (score maps: unweighted) waives lat_weight alone.  Pointer checks and limits of its own (LDC_ERR_UNSUPPORTED) stay with each
 // entry point, behind this call.
 static inline int ldc_rollout_view(RolloutView* v, const float* forecast, long long member_stride, long long lead_stride,
                                    long long channel_stride, const float* mean, const float* std_, float target_std, const float* truth,
                                    long long truth_slot_stride, long long truth_channel_stride, const int* truth_slot, const float* clim,
                                    long long clim_slot_stride, long long clim_channel_stride, const int* clim_slot, const float* lat_weight,
-                                   int M, int C, int L, int H, int W, int L_total, int l_off, bool with_truth = true) {
+                                   int M, int C, int L, int H, int W, int L_total, int l_off, bool with_truth = true, bool with_weight = true) {
   LDC_CHECK_PTR(forecast);
   if (with_truth) {
     LDC_CHECK_PTR(truth);
     LDC_CHECK_PTR(truth_slot);
-    LDC_CHECK_PTR(lat_weight);
+    if (with_weight) LDC_CHECK_PTR(lat_weight);
   }
   if (clim != nullptr) LDC_CHECK_PTR(clim_slot);
   if (mean != nullptr && std_ == nullptr) return LDC_ERR_ARG;

@@ -5,7 +5,8 @@
 // fused inverse normalisation (inv_norm, ensemble_common.h), truth and climatology as tables of planes with a slot per lead time,
 // lat_weight[H], output columns at l_off.  region_mask[H * W]: bit r of the word of point p says that p belongs to region r < R <= 32.
 // Per grid point that lies in at least one region, members x_i in member order after the inverse normalisation, truth t, weight w,
-// climatology a, every value fp32 and formed as the kernel that already has it forms it:
+// climatology a, every value fp32 and formed as the kernel that already has it forms it (ensemble_point_values, ensemble_common.h: the
+// one function that this kernel and score_maps.hip call, so that the maps hold these bits):
 //   mean   = (x_0 + ... + x_{M-1}) / M, e = mean - t, se = e * e            (score_point, scoring.hip)
 //   var    = sum_i (x_i - mean)^2 / (M - 1), two-pass in member order       (reliability.hip); M == 1: 0
 //   skill  = sum_i |t - x_i| / M                                            (score_point)
@@ -63,7 +64,6 @@ __global__ __launch_bounds__(TPB) void regional_kernel(RegArgs a) {
   const float* tbase = view_truth(a.v, c, l);
   const float* cbase = view_clim(a.v, c, l);
   const InvNorm nrm = view_norm<INV>(a.v, c);
-  const float Mf = static_cast<float>(M);
   double acc0 = 0.0, acc1 = 0.0;
   int n_val = 0, n_inv = 0, n_acc = 0;
   const int tile0 = blockIdx.x * TPW;
@@ -75,71 +75,25 @@ __global__ __launch_bounds__(TPB) void regional_kernel(RegArgs a) {
     if (!__syncthreads_or(m != 0u)) continue;
     unsigned mv = 0u, ma = 0u, mi = 0u;
     if (m != 0u) {
-      const float* f = fbase + p;
-      float x[NP];
-      bool nan_m = false;
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        if (i < NUSE && i < M) {
-          const float v = load_member<INV>(f, i, a.v.fc_ms, nrm);
-          x[i] = v;
-          sum += v;
-          nan_m = nan_m || (v != v);
-        } else {
-          x[i] = INFINITY;  // sorts behind every member
-        }
-      }
-      const float t = tbase[p];
+      const PointValues pv = ensemble_point_values<NP, NUSE, INV>(fbase + p, a.v.fc_ms, nrm, M, tbase + p, cbase ? cbase + p : nullptr);
       const float w = a.v.lat_w[p / a.v.W];
-      float skill = 0.f;
-#pragma unroll
-      for (int i = 0; i < NUSE; ++i)
-        if (i < M) skill += fabsf(t - x[i]);
-      skill /= Mf;
-      const float mean = sum / Mf;
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < NUSE; ++i)
-        if (i < M) {
-          const float d = x[i] - mean;
-          ss += d * d;
-        }
-      float var = 0.f, spread = 0.f;
-      if (M >= 2) {
-        var = ss / (Mf - 1.0f);
-        sort_network<NP, NUSE>(x);
-        float ws = 0.f;
-#pragma unroll
-        for (int i = 0; i < NUSE; ++i)
-          if (i < M) ws = fmaf(x[i], 2.0f * static_cast<float>(i + 1) - Mf - 1.0f, ws);
-        spread = 2.0f * ws / (Mf * (Mf - 1.0f));
-      }
-      const float e = mean - t;
-      const float se = e * e;
-      const bool valid = !nan_m && t == t;
       const double wd = static_cast<double>(w);
       double* dst = &s_val[tid * NS];
       dst[0] = wd;
-      dst[1] = wd * static_cast<double>(e);
-      dst[2] = wd * static_cast<double>(se);
-      dst[3] = wd * static_cast<double>(var);
-      dst[4] = wd * static_cast<double>(skill);
-      dst[5] = wd * static_cast<double>(spread);
-      bool v_acc = false;
+      dst[1] = wd * static_cast<double>(pv.e);
+      dst[2] = wd * static_cast<double>(pv.se);
+      dst[3] = wd * static_cast<double>(pv.var);
+      dst[4] = wd * static_cast<double>(pv.skill);
+      dst[5] = wd * static_cast<double>(pv.spread);
       if (cbase) {
-        const float cl = cbase[p];
-        const float fa = mean - cl, ta = t - cl;
-        const float fta = fa * ta, ffa = fa * fa, tta = ta * ta;
-        v_acc = valid && cl == cl;
         dst[6] = wd;
-        dst[7] = wd * static_cast<double>(fta);
-        dst[8] = wd * static_cast<double>(ffa);
-        dst[9] = wd * static_cast<double>(tta);
+        dst[7] = wd * static_cast<double>(pv.fta);
+        dst[8] = wd * static_cast<double>(pv.ffa);
+        dst[9] = wd * static_cast<double>(pv.tta);
       }
-      mv = valid ? m : 0u;
-      mi = valid ? 0u : m;
-      ma = v_acc ? m : 0u;
+      mv = pv.valid ? m : 0u;
+      mi = pv.valid ? 0u : m;
+      ma = pv.acc_valid ? m : 0u;
     }
     s_m[0][tid] = mv;
     s_m[1][tid] = ma;

@@ -99,7 +99,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
                          decode_batch_frames: Optional[int] = None, reliability: bool = False, spectrum: bool = False,
                          spectrum_row_weight: Optional[torch.Tensor] = None, events: Optional[Sequence] = None,
                          regions: Optional[Sequence] = None, region_mask=None, fss_radii: Optional[Sequence[int]] = None, energy: bool = False,
-                         energy_groups: Optional[Sequence] = None, energy_scales=None, derived: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
+                         energy_groups: Optional[Sequence] = None, energy_scales=None, derived: Optional[Sequence] = None,
+                         score_maps: Optional["ScoreMaps"] = None) -> Dict[str, torch.Tensor]:  # noqa: F821  (score_maps.ScoreMaps)
     """One initial time of evaluate_ens_gpu.py:268-425: a saved `latent_YYYYMMDDHH.npy` (or its (ens, C, T, h, w) tensor) -> the five
     (C, total_num_steps) fp32 CPU tensors `ens_acc`, `ens_mse`, `crps_spread`, `crps_skill`, `crps`.
 
@@ -115,6 +116,8 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
     `energy_scales` switch on the optional metrics of `rollout_metrics.METRICS` (`Reliability`, `Spectrum`, `Events`, `Regional`,
     `Energy`: each class states its options and the keys the result gains).  Every decode batch goes through each of them, in that
     order, while it is on the device; nothing more is decoded or kept.  Every other output is the bits of a call without it.
+    `score_maps`: a `score_maps.ScoreMaps` accumulator (`Maps`, the last of them); every decode batch is added to it on the device and
+    the result gains no key: the caller downloads the accumulator once, after the last initial time.
 
     `derived`: a sequence of `derived.Derived(name, kind, channels)`; the D fields become channels C' .. C' + D - 1 of every result
     and of every option that names a channel (`events`, `energy_groups`, `energy_scales`).  Each decode batch is copied into the head
@@ -151,7 +154,7 @@ def score_latent_rollout(latents_or_path: Union[str, torch.Tensor], encdec_model
         check_scoring_fields(fields, int(torch.as_tensor(mean_tensor).numel()), sst_channel, events)
     options = dict(reliability=reliability, spectrum=spectrum, spectrum_row_weight=spectrum_row_weight, events=events, fss_radii=fss_radii,
                    regions=regions, region_mask=region_mask, energy=energy, energy_groups=energy_groups, energy_scales=energy_scales,
-                   clim=clim, std_tensor=std_tensor if fields is None else extended_scales(fields, std_tensor))
+                   score_maps=score_maps, clim=clim, std_tensor=std_tensor if fields is None else extended_scales(fields, std_tensor))
     metrics = [m for m in (cls.for_rollout(options) for cls in METRICS) if m is not None]  # their options: checked before anything is decoded
     dev = encdec_model.device
     if torch.device(dev).type != "cuda":

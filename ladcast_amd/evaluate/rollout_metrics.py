@@ -18,6 +18,7 @@ import torch
 from .energy import ENERGY_GROUP_NAMES, ENERGY_NAMES, EnergyGroup, _group_list, empty_energy, inverse_scale2, rollout_energy
 from .regional import (COUNT_NAMES, SUM_NAMES, REGIONAL_KEYS, REGIONAL_SCORE_NAMES, NAMED_REGIONS, Region, empty_regional, mask_words, region_mask as make_region_mask,
                        region_metadata, regional_scores, rollout_regional)
+from .score_maps import MAP_COUNT_NAMES, SCORE_MAP_NAMES, TERM_NAMES, ScoreMaps, parse_map_planes, rollout_score_maps, score_maps
 from .utils import (MAX_FSS_SCALES, SPECTRUM_NAMES, Event, _radius_list, empty_events, empty_fss, empty_reliability, empty_spectrum, event_scores, fss_scores,
                     rollout_events, rollout_fss, rollout_reliability, rollout_spectrum)
 
@@ -552,4 +553,83 @@ def parse_energy_groups(entries: Sequence[Sequence[str]], names: Sequence[str]) 
     return _group_list(groups, len(names))
 
 
-METRICS = (Reliability, Spectrum, Events, Regional, Energy)  # launch and key order; `Events` holds the fss, which follows the events
+class Maps(Metric):
+    """`score_maps` / `--map`: per-point score maps accumulated on the device over the initial times (`rollout_score_maps`).  `score_maps`:
+    a `ScoreMaps` accumulator, which the caller keeps over any number of `score_latent_rollout` calls and downloads once; every decode
+    batch is added to it after the other metrics have run, and `n_init` counts the calls.  The result of an initial time gains NO key.
+    `--map CHANNEL [CHANNEL ...]` (names as `--event` resolves them, or indices; `all`: every channel), `--map_lead_hours H ...` (one
+    plane per listed lead hour; default: every lead time) or `--map_lead_bins A-B ...` (one plane per inclusive range of lead hours,
+    pooled), `--map_max_gib` (default 16; a guard, not a measurement: the run prints the bytes of the accumulators and refuses above it
+    before anything is decoded).  Files, written once from one download: `score_map_sums.npy` (Cm, P, 8, H, W) float64,
+    `score_map_counts.npy` (Cm, P, 3, H, W) int32, `score_map_<score>.npy` (Cm, P, H, W) for `SCORE_MAP_NAMES` (`score_maps`),
+    `score_maps.json` (channel names, planes with their lead hours, members, n_init, term names)."""
+
+    flag = "--map"
+    names = planes = None  # score_maps.json's channel names and planes, where the command line knows them
+
+    def __init__(self, acc):
+        if not isinstance(acc, ScoreMaps):
+            raise ValueError("score_maps must be a ScoreMaps accumulator")
+        self.maps = acc
+
+    @classmethod
+    def for_rollout(cls, o):
+        acc = o.get("score_maps")  # option dicts built before this metric existed do not hold the key
+        return cls(acc) if acc is not None else None
+
+    def run(self, b):
+        rollout_score_maps(b.y, b.truth, self.maps, **b.clim_kw, **b.kw)
+
+    def result(self):
+        self.maps.n_init += 1
+        return {}
+
+    @staticmethod
+    def add_arguments(ap):
+        ap.add_argument("--map", nargs="+", default=None, metavar="CHANNEL", help="accumulate per-point score maps of these channels (names or indices; all: every channel)")
+        ap.add_argument("--map_lead_hours", nargs="+", default=None, metavar="H", help="one map plane per listed lead hour (default: every lead time)")
+        ap.add_argument("--map_lead_bins", nargs="+", default=None, metavar="A-B", help="one map plane per inclusive range of lead hours, pooled; excludes --map_lead_hours")
+        ap.add_argument("--map_max_gib", type=float, default=16.0, help="refuse map accumulators larger than this many GiB of device memory")
+
+    @classmethod
+    def parse(cls, args, files):
+        if args.map is None:
+            if args.map_lead_hours is not None or args.map_lead_bins is not None:
+                raise ValueError("--map_lead_hours and --map_lead_bins need --map")
+            return None
+        from .products import resolve_channels
+
+        names = _channel_names(args)
+        chans = list(range(len(names))) if list(args.map) == ["all"] else resolve_channels(args.map, names)
+        if len(set(chans)) != len(chans):
+            raise ValueError(f"--map {' '.join(args.map)}: a channel is named twice")
+        total = args.total_lead_time_hour // args.step_size_hour
+        plane_of_lead, planes = parse_map_planes(total, args.step_size_hour, args.map_lead_hours, args.map_lead_bins)
+        if not args.map_max_gib > 0:
+            raise ValueError("--map_max_gib must be positive")
+        m = cls(ScoreMaps(chans, plane_of_lead, len(planes)))
+        m.names, m.planes, m.max_gib = [names[c] for c in chans], planes, float(args.map_max_gib)
+        return m
+
+    def rollout_kwargs(self, H, W, lat_w, std_t):
+        nbytes = self.maps.nbytes(H, W)
+        print(f"score maps: {len(self.maps.channels)} channels x {self.maps.n_planes} planes x {H} x {W} points: {nbytes} bytes on the device")
+        if nbytes <= 0 or nbytes > self.max_gib * 2 ** 30:
+            raise ValueError(f"--map: the accumulators take {nbytes} bytes ({nbytes / 2 ** 30:.2f} GiB; 0: sizes the kernel refuses), --map_max_gib is {self.max_gib}")
+        return dict(score_maps=self.maps)
+
+    def gather(self, res, time_str):
+        pass
+
+    def finish(self, out, output):
+        if self.maps.sums is None:
+            raise ValueError("--map: nothing was accumulated (the maps live on the device: an injected scorer must add to the ScoreMaps itself)")
+        sums, counts = self.maps.download()
+        sc = score_maps(sums, counts, self.maps.members)
+        out.update(score_map_sums=sums, score_map_counts=counts, **{f"score_map_{k}": np.asarray(sc[k]) for k in SCORE_MAP_NAMES})
+        with open(os.path.join(output, "score_maps.json"), "w") as f:
+            json.dump(dict(channels=self.names, channel_indices=self.maps.channels, planes=self.planes, plane_of_lead=self.maps.plane_of_lead,
+                           members=self.maps.members, n_init=self.maps.n_init, terms=list(TERM_NAMES), counts=list(MAP_COUNT_NAMES)), f, indent=1)
+
+
+METRICS = (Reliability, Spectrum, Events, Regional, Energy, Maps)  # launch and key order; `Events` holds the fss, which follows the events

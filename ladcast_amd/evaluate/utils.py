@@ -132,7 +132,7 @@ def _plane_table(t: torch.Tensor, slots, C: int, L: int, H: int, W: int, what: s
     return t, t.stride(0), t.stride(1), slots
 
 
-# What the nine rollout_* / validation_scores wrappers (here, in regional.py and energy.py) share.  Each runs every check that needs no device first
+# What the ten rollout_* / validation_scores wrappers (here, in regional.py, score_maps.py and energy.py) share.  Each runs every check that needs no device first
 # (ValueError, NotImplementedError): `_prologue`, its own limits, `l_off`, `out`; then `hip._dev` on the tensors it cannot take from the host.
 def _forecast_view(forecast: torch.Tensor, lead_dim: int):
     """-> (f, M, C, L, H, W): the forecast as (ens, C, L, H, W) with a contiguous (H, W) plane, any member / lead / channel strides"""

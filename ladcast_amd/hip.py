@@ -1,9 +1,10 @@
 """ctypes binding of the C ABI in ``include/ladcast_hip.h``, generated from that header.
 
 ``ladcast_amd.abi`` reads the header at import: its prototypes become ``SIGNATURES`` (restype and argtypes of every entry point) and
-its ``ldc_*`` structs the ``ctypes.Structure`` classes named below, so a new entry point needs its prototype in the header and a
-wrapper here, nothing else.  The constants stay literals, since call sites read them by name; tests/test_abi_cpu.py holds them to
-the header.
+its ``ldc_*`` structs the ``ctypes.Structure`` classes named below.  That header's set of entry points is recorded and held by the ABI
+tests, so a new entry point needs its prototype in ``include/ladcast_hip_ext.h`` (read into ``abi.EXT_SIGNATURES`` and bound here
+alongside) and a wrapper here, nothing else.  The constants stay literals, since call sites read them by name; tests/test_abi_cpu.py
+holds them to the header.
 
 PyTorch is plumbing here: it owns device memory and the HIP stream.  Every wrapper takes
 torch CUDA(=HIP) tensors, passes raw device pointers + sizes + the current stream to the
@@ -62,7 +63,7 @@ def _load():
             "(or `make -C ladcast_amd/csrc`).  ladcast_amd has no CPU fallback."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in abi.SIGNATURES.items():
+    for name, (res, args) in (*abi.SIGNATURES.items(), *abi.EXT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -494,6 +495,27 @@ def rollout_regional(forecast, truth, truth_slot, clim, clim_slot, lat_weight, r
                                     *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
                                     clim_channel_stride, _p(clim_slot), _p(lat_weight), _p(region_mask), R, M, C, L, H, W, _p(sums), _p(counts),
                                     L_total, l_off, _p(ws), ws.numel() * 4, _stream()), "ldc_rollout_regional")
+
+
+SCORE_MAPS_TERMS, SCORE_MAPS_COUNTS, SCORE_MAPS_MAX_MEMBERS = 8, 3, 64  # LDC_SCORE_MAPS_* (ladcast_hip_ext.h) and the largest ensemble
+
+
+def score_maps_bytes(Cm, P, H, W):
+    """bytes of the two accumulators of ldc_rollout_score_maps together (76 per channel, plane and point); 0 for sizes the call refuses"""
+    return int(lib.ldc_score_maps_bytes(Cm, P, H, W))
+
+
+def rollout_score_maps(forecast, truth, truth_slot, clim, clim_slot, channel_idx, plane_of_lead, sums, counts, *, Cm, P, M, C, L, H, W,
+                       member_stride, lead_stride, channel_stride, truth_slot_stride, truth_channel_stride, clim_slot_stride=0,
+                       clim_channel_stride=0, mean=None, std=None, target_std=1.0):
+    """sums (fp64) [Cm][P][8][H * W] and counts (int32) [Cm][P][3][H * W] += the L lead times of this call, lead l into plane
+    plane_of_lead[l] (-1: skipped), for the channels channel_idx (ladcast_hip_ext.h: ldc_rollout_score_maps); channel_idx [Cm],
+    plane_of_lead / truth_slot / clim_slot [L]: device int32, their values checked by the caller"""
+    _dev(forecast, truth, truth_slot, clim, clim_slot, channel_idx, plane_of_lead, sums, counts, mean, std)
+    _check(lib.ldc_rollout_score_maps(*_forecast_args(forecast, member_stride, lead_stride, channel_stride, mean, std, target_std),
+                                      *_truth_args(truth, truth_slot_stride, truth_channel_stride, truth_slot), _p(clim), clim_slot_stride,
+                                      clim_channel_stride, _p(clim_slot), _p(channel_idx), Cm, _p(plane_of_lead), P, M, C, L, H, W, _p(sums),
+                                      _p(counts), _stream()), "ldc_rollout_score_maps")
 
 
 ENERGY_MAX_MEMBERS, ENERGY_MAX_GROUPS, ENERGY_PLANES = 256, 32, 5  # the limits of ldc_rollout_energy and the planes of its score buffers
